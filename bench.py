@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- particle-scan evaluations per second of the MI355X particle-filter SLAM step.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
       N > 1: either started by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
       (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or started plainly -- then bench.py launches its own N ranks
       (one child process per GPU with the same environment variables set) and relays rank 0's line.
@@ -16,6 +16,11 @@ BASELINE configs[3]'s per-GPU share is `--particles 125000 --map-points 500000`.
 
 One JSON line on rank 0:  value = particles scored per second over the whole job, with the map, particles and
 all state resident in HBM (the 4.3 KB scan per frame is the step API's input and is inside the timed region).
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step and the workload).
+--dump-outputs DIR writes what the last timed step left for a caller (pose, particles, map, trace) as DIR/<name>.npy.
+--full adds everything below -- frame probe, steady-state window, census replay and roofline, collectives, CPU baseline,
+long run, per-phase split, extras --, all of it after the timed window, which is the same as in a plain run.
 
 "roofline" prices the dominant kernel (the scan-match kernel) against the resource that binds it -- the CU's gather path (texture
 addresser: 4 lane addresses per clock for 64-bit and wider loads, i.e. 64 B/clk per CU for the 16-byte node records).
@@ -61,7 +66,7 @@ def parse():
     ap.add_argument("--particles", type=int, default=100000, help="particles per GPU")
     ap.add_argument("--map-points", type=int, default=100000)
     ap.add_argument("--cpu-sample", type=int, default=0, help="particles in the CPU-baseline sample (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs, the long-run leg and the extras (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="the --full run without the CPU legs, the long-run leg and the extras (profiling runs; implies --full)")
     ap.add_argument("--pmc-file", default="", help="rocprofv3 PMC summary to take roofline.traffic from (default: newest matching profiles/r*_pmc_score_kd*.json)")
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--backend", default="", help="torch.distributed backend of the process group (default: gloo with --collectives rccl -- the group only "
@@ -74,7 +79,43 @@ def parse():
                     help="who issues the frame's all-gathers: rccl = libpfslam_mgpu.so launches them straight into the frame's own streams (default); "
                          "torch = torch.distributed with the frame's stream as the current stream (debugging; what --backend gloo / --same-device use)")
     ap.add_argument("--dry-collectives", action="store_true", help="also time the frame's collectives on their own (per-rank wall times in the line); with one rank: the fields, no traffic")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also the measurements beyond the headline figure (frame probe, steady state, census replay + "
+                    "roofline, collectives, CPU baseline, long run, phases, extras); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (pose, particles, map, trace) "
+                    "as DIR/<name>.npy, float32 / float64, at most 64 MB in all (a fixed seeded row sample beyond that)")
+    a = ap.parse_args()
+    a.full = a.full or a.no_cpu_baseline
+    return a
+
+
+DUMP_LIMIT = 64 * 1000 * 1000   # bytes, all files together
+
+
+def dump_outputs(out_dir, pose, particles, nodes, trace):
+    """The state a caller of pfslam_step reads back after the last timed step, as float32 / float64 .npy files.  Rows of the
+    particle and map arrays beyond the size limit are thinned to a fixed, seeded sample; `<group>_index.npy` then names the rows."""
+    groups = {
+        "particles": {"particles": np.stack([particles[k].astype(np.float32) for k in ("x", "y", "theta", "w")], axis=1)},
+        "map": {"map_points": np.stack([nodes[k].astype(np.float32) for k in ("x", "y", "z", "w")], axis=1),
+                "map_links": np.stack([nodes[k].astype(np.float64) for k in ("axis", "left", "right", "parent")], axis=1)},
+    }
+    fixed = {"pose": np.asarray(pose, np.float32),
+             "trace": np.array([trace[k] for k in ("best", "resampled", "n_wall", "n_free", "n_insert", "neff", "kd_size")], np.float64)}
+    fixed_bytes = sum(a.nbytes for a in fixed.values())
+    scale = 1.0
+    if fixed_bytes + sum(a.nbytes for g in groups.values() for a in g.values()) > DUMP_LIMIT:   # sampled rows carry an 8-byte index each
+        scale = 0.99 * (DUMP_LIMIT - fixed_bytes) / sum(a.nbytes + 8 * len(a) / len(g) for g in groups.values() for a in g.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in fixed.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    for gname, arrays in groups.items():
+        rows = len(next(iter(arrays.values())))
+        if scale < 1.0:
+            idx = np.sort(np.random.RandomState(12345).choice(rows, int(rows * scale), replace=False))
+            arrays = {k: a[idx] for k, a in arrays.items()}
+            np.save(os.path.join(out_dir, gname + "_index.npy"), idx.astype(np.float64))
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def host_cpu():
@@ -353,9 +394,11 @@ def main():
     n_global = n_local * world
     pts, segs = pkg.synth.make_map_points(a.map_points, seed=1)
     tree = pkg.kd_create(pts)
-    long_run = not a.no_cpu_baseline
+    long_run = a.full and not a.no_cpu_baseline
     # long-run leg: filler up to the next frame % 100 == 6, 100 timed frames, 20 frames for the phase split
-    n_frames = a.warmup + 3 * a.steps + (100 + 100 + 20 if long_run else 0)   # (+ 2 x steps: the frame-probe leg and the steady-state window; long run: filler up to the next frame % 100 == 6, then 100 + 20)
+    n_frames = a.warmup + a.steps
+    if a.full:
+        n_frames += 2 * a.steps + (100 + 100 + 20 if long_run else 0)   # (the frame-probe leg and the steady-state window; long run: filler up to the next frame % 100 == 6, then 100 + 20)
 
     def one_scan(f):
         return pkg.synth.make_scan(segs, (0.002 * f, 0.001 * f, 0.0004 * f), seed=2000 + f)
@@ -363,7 +406,9 @@ def main():
     with ThreadPoolExecutor(max_workers=host_cpu()[0]) as pool:  # numpy releases the GIL in the ray-casting ufuncs
         scans = list(pool.map(one_scan, range(n_frames)))
 
-    cap = a.map_points + (1 << 18)
+    # map capacity: a frame inserts at most one node per beam (the library's wall list holds n_beams), so the frames this run steps bound the
+    # growth; at least the 2^18 spare nodes of a short run, at most the reference's KD_MAX_SIZE (kernel.cu:77)
+    cap = a.map_points + min(max(1 << 18, 1081 * n_frames), 10000000)
 
     fallback = {}   # native RCCL asked for and not available on every rank: {"native": False, "reason": ...}
 
@@ -494,6 +539,8 @@ def main():
     eng.set_timing(0)
     trace = eng.trace()
     pose_timed = np.array(eng.pose, np.float32)
+    if a.dump_outputs and rank == 0:   # (a sharded job: rank 0's particles; pose and map are replicated)
+        dump_outputs(a.dump_outputs, pose_timed, eng.particles(), eng.map(), trace)
     # how the timed frames ran: the round-5 frame (four in-order streams), its cross-stream edges as device-word gates or as events (the
     # start-up self-test decides; a second handle in the process withdraws the gates), one-stream mode
     fm = e0.frame_mode()
@@ -508,13 +555,13 @@ def main():
     # ---- where the frame's time goes: the next `steps` frames on the SAME handle with the frame probe on (pfslam_set_probe: the first thread
     # of every launch of a round-5 frame stores the wall clock; no events, no profiler) -- outside the timed region
     frame_probe, probe_frames = None, 0
-    if not distributed:
+    if a.full and not distributed:
         try:
-            e0.set_probe(a.steps + 8)
+            e0.set_probe(min(a.steps + 8, 4096))   # (a ring of at most 4096 frames: a longer leg keeps its last 4096)
             for k in range(a.steps):
                 eng.step(frame, scans[a.warmup + a.steps + k]); frame += 1; probe_frames += 1
             eng.synchronize()
-            names, tp, _ = e0.probe(a.steps)
+            names, tp, _ = e0.probe(min(a.steps, 4096))
             e0.set_probe(0)
             if len(tp) and "C scan-match" in names:
                 sc, rd = names.index("C scan-match"), names.index("C reduce")
@@ -528,7 +575,7 @@ def main():
                                    "launch_start_us_after_scan_match_start": {names[k]: float(np.nanmean(rel[:, k])) for k in range(len(names)) if not np.all(np.isnan(rel[:, k]))},
                                    "note": "chain = start of a frame's reduce -> start of the next frame's scan-match kernel: what sits between two scan-match "
                                            "kernels (reduce, walls + insert, cell rows, the edge to the particle chain); wall-clock stamps of the launches' first "
-                                           "threads over the %d frames BEHIND the timed window, same handle" % a.steps}
+                                           "threads over the last %d frames BEHIND the timed window, same handle" % len(tp)}
         except Exception as e:  # the probe must never break the contract line
             frame_probe = {"error": repr(e)}
     # ---- steady state: the same K steps once more, further into the run (every rank takes part).  The contract window above starts right
@@ -536,7 +583,7 @@ def main():
     # loop runs at from then on.  Reported beside `value`, never in its place.
     steady = None
     k_steady = a.warmup + a.steps + probe_frames
-    if k_steady + a.steps <= n_frames:
+    if a.full and k_steady + a.steps <= n_frames:
         dts = timed(k_steady, a.steps, frame)
         steady = {"value": n_global * a.steps / dts, "ms_per_step": dts / a.steps * 1e3, "frames": "%d..%d" % (frame, frame + a.steps - 1), "unit": "particle-scan evals/s"}
         frame += a.steps
@@ -545,19 +592,20 @@ def main():
     # ---- census replay: what exactly did the timed launches issue?  A second handle steps through the same frames -- the frame
     # loop is deterministic, so its particles, scans and map are the timed run's, bit for bit (checked on the pose) -- with the
     # counting instantiation of the scan-match kernel behind every scoring pass (pfslam_set_census).  Every rank takes part.
-    rep = make_engine()
-    r0 = rep.eng if hasattr(rep, "eng") else rep
-    r0.set_census(True)
-    for k in range(a.warmup + a.steps):
-        rep.step(FIRST_FRAME + k, scans[k])
-    rep.synchronize()
-    census_all = r0.census_log()
-    replay_identical = bool((np.array(rep.pose, np.float32).view(np.int32) == pose_timed.view(np.int32)).all())
-    r0.set_census(False)
-    r0.close()
-    del rep, r0
+    if a.full:
+        rep = make_engine()
+        r0 = rep.eng if hasattr(rep, "eng") else rep
+        r0.set_census(True)
+        for k in range(a.warmup + a.steps):
+            rep.step(FIRST_FRAME + k, scans[k])
+        rep.synchronize()
+        census_all = r0.census_log()
+        replay_identical = bool((np.array(rep.pose, np.float32).view(np.int32) == pose_timed.view(np.int32)).all())
+        r0.set_census(False)
+        r0.close()
+        del rep, r0
 
-    coll = time_collectives() if (world > 1 or a.dry_collectives) else None   # every rank takes part
+    coll = time_collectives() if ((a.full and world > 1) or a.dry_collectives) else None   # every rank takes part
     out = None
     if rank == 0:
         ms_per_step = dt / a.steps * 1e3
@@ -586,6 +634,7 @@ def main():
             out["collectives"] = coll
         if a.cloud_sigma > 0:
             out["config"]["cloud_sigma_m"] = a.cloud_sigma
+    if out is not None and a.full:
         import oracle_lib as O
         # ---- roofline of the dominant kernel (rank 0's launches) -------------------------------------
         tree_end = np.ascontiguousarray(e0.map(), dtype=O.NODE_DTYPE)
@@ -738,7 +787,7 @@ def main():
         }
 
     # ---- the same step over a whole balance cycle (every rank takes part; rank 0 reports) ----------
-    if dist is not None:
+    if dist is not None and a.full:
         dist.barrier()   # rank 0 has just put its report together: the others enqueue nothing while it does (a frame's stream gates wait behind the collectives)
     if long_run:
         # continue to the next frame % 100 == 6, then time exactly 100 frames: one KDTree::Balance (frame % 100 == 5) inside
@@ -772,7 +821,7 @@ def main():
                           "note": "KDTree::Balance once per node: rank 0 re-builds the map on the host, the device arrays (28 B per node) "
                                   "are broadcast, the other ranks adopt them (include/pfslam.h, pfslam_shard_balance_*)"}
     if out is not None:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             import oracle_lib as O
             out["extras"] = extras(pkg, O, tree, pts, scans[0], local_rank)
         print(json.dumps(out))

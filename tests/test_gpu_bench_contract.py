@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_line_has_contract_fields():
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                                    "--particles", "5000", "--map-points", "20000", "--cpu-sample", "256"], cwd=ROOT).decode()
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -51,9 +51,44 @@ def test_bench_json_line_has_contract_fields():
     assert abs(d["value"] - 5000 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run times the steps and prints the headline line without the --full legs; --dump-outputs writes the state the
+    last timed step left as float32 / float64 .npy files, the same bit for bit in a --full run of the same arguments (the
+    timed window and its inputs do not depend on --full)."""
+    import numpy as np
+    args = ["--steps", "3", "--warmup", "1", "--particles", "5000", "--map-points", "20000"]
+    dumps = {}
+    for mode in ("plain", "full"):
+        extra = ["--full", "--no-cpu-baseline"] if mode == "full" else []
+        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py")] + args + extra +
+                                      ["--dump-outputs", str(tmp_path / mode)], cwd=ROOT, timeout=600).decode()
+        lines = [l for l in out.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert abs(d["value"] - 5000 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
+        if mode == "plain":
+            assert not {"roofline", "cpu_baseline", "long_run", "steady_state", "frame", "extras"} & set(d), sorted(d)
+        else:
+            assert d["roofline"]["launches"] == 3 and d["roofline"]["census"]["replay_identical"] is True
+        files = sorted(os.listdir(str(tmp_path / mode)))
+        assert {"pose.npy", "particles.npy", "map_points.npy", "map_links.npy", "trace.npy"} <= set(files), files
+        assert sum(os.path.getsize(str(tmp_path / mode / f)) for f in files) <= 64 * 1000 * 1000
+        dumps[mode] = {f: np.load(str(tmp_path / mode / f)) for f in files}
+        for f, v in dumps[mode].items():
+            assert v.dtype in (np.float32, np.float64), (f, v.dtype)
+    p = dumps["plain"]
+    assert p["particles.npy"].shape == (5000, 4) and p["map_points.npy"].shape[0] == p["trace.npy"][6] >= 20000
+    assert p.keys() == dumps["full"].keys()
+    for f in p:
+        assert p[f].tobytes() == dumps["full"][f].tobytes(), f
+
+
 def _torchrun(nproc, port, *bench_args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3",
+           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(nproc), "--steps", "3",
            "--warmup", "1", "--particles", "4096", "--map-points", "20000"] + list(bench_args)
     # (the process-group bootstrap has been seen to hang on some leases -- 2 of 8 boxes in round 5, never
     # reproducible in a loop of the same command on another box --: a watchdog inside bench.py, a bounded wait here, and one retry on a fresh port)
@@ -95,7 +130,7 @@ def test_bench_under_torchrun_two_ranks_on_one_gpu():
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` WITHOUT torchrun: bench.py starts the two ranks itself (gloo, both on GPU 0) and rank 0's
     line is the only one printed."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--particles", "4096",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--particles", "4096",
            "--map-points", "20000", "--backend", "gloo", "--same-device"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.check_output(cmd, cwd=ROOT, stderr=subprocess.STDOUT, timeout=600, env=env).decode()
@@ -113,7 +148,7 @@ def test_roofline_census_agrees_with_committed_pmc():
     import glob
     if not glob.glob(os.path.join(ROOT, "profiles", "r0[3-9]_pmc_score_kd.json")):
         pytest.skip("no round-3+ PMC summary of the default workload committed yet")
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"], cwd=ROOT, timeout=900).decode()
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"], cwd=ROOT, timeout=900).decode()
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
     r = d["roofline"]
     assert r["census"]["replay_identical"] is True and r["launches"] == 20
