@@ -60,7 +60,7 @@ enum { PF_CS_COUNT = 0, PF_CS_POOL, PF_CS_SNAP, PF_CS_PAD3, PF_CS_LIST_CAP, PF_C
        PF_CS_NONE, PF_CS_CUR_FRESH, PF_CS_CUR_EXT, PF_CS_CUR_REUSED, PF_CS_CUR_CLAIMED, PF_CS_WORDS = 32,
        // The window's corner lives 512 bytes away from the counters: every wave of the scan-match kernel reads it, and in the frame
        // loops the marking pass runs BESIDE that kernel, adding to the list counter -- on the same 128-byte line the 131 k reads
-       // queued behind those atomics and the scan-match kernel lost 27 us (0.373 -> 0.400 ms; found by elimination: PFSLAM_CELLS_MODE)
+       // queued behind those atomics and the scan-match kernel lost 27 us (0.373 -> 0.400 ms; found by elimination, with the cell passes made synchronous)
        PF_CS_OX = 128, PF_CS_OY = 129, PF_CS_ALLOC = 256 };
 #define PF_CF_LIST_FULL 1   /* more cells claimed than PF_CELL_LIST_CAP: the rest takes the generic traversal until the wipe */
 #define PF_CF_POOL_FULL 2   /* row pool exhausted */
@@ -80,9 +80,7 @@ enum { PF_CS_COUNT = 0, PF_CS_POOL, PF_CS_SNAP, PF_CS_PAD3, PF_CS_LIST_CAP, PF_C
 #define PF_REC_POOL 76 /* [76] first pool slot of the cell's four rows, [77] slots allocated: an extension re-cuts IN PLACE while the rows fit */
 #define PF_REC_LAST 80 /* [80 .. 83] the four table words this record published last: what the next publication replaces (its accounts are
                           closed from here -- the table words themselves are then plain stores, not exchanges whose answer the wave waits for) */
-#ifndef PF_ROW_GROW
-#define PF_ROW_GROW 2 /* slots allocated beyond what the first cut needs (0 / 1 / 4: no difference beyond the run-to-run noise, ab_row_grow.sh) */
-#endif
+#define PF_ROW_HEADROOM 2 /* slots allocated beyond what the first cut needs (0 / 1 / 4: no difference beyond the run-to-run noise, ab_row_grow.sh) */
 #define PF_RF_FRESH 1 /* walked under the scan-match kernel: rows not cut yet */
 #define PF_RF_DEAD 2  /* no rows until the next wipe (too many candidates, a non-finite node on the path) */
 #define PF_RF_ROVER 4 /* re-descent candidates did not fit: rows say n2 = 15 (generic tail), re-descent links are not watched */
@@ -486,13 +484,7 @@ __global__ __launch_bounds__(64) void k_cells_update(pf::KdView tree, CellGeom g
         int2 pre_pool = make_int2(0, 0);
         int4 pre_last = make_int4(0, 0, 0, 0);
         int pre_cell = 0;
-#ifndef PF_CU_HOIST
-#define PF_CU_HOIST 1 /* 0: the lazy loads of round 4 (A/B, bisecting) */
-#endif
-#ifndef PF_CU_LAST
-#define PF_CU_LAST 1 /* 0: the table words are exchanged and the answers close the accounts (A/B, bisecting) */
-#endif
-        constexpr bool HOIST = PUBLISH && PF_CU_HOIST != 0;
+        constexpr bool HOIST = PUBLISH;
         if (HOIST) {
 #pragma unroll
             for (int q = 0; q < 4; q++) pre_ct[q] = pre_cand[q] = pre_par[q] = make_int4(-1, -1, -1, -1);
@@ -699,10 +691,7 @@ __global__ __launch_bounds__(64) void k_cells_update(pf::KdView tree, CellGeom g
                 bounds(cxlo, cxhi, cylo, cyhi, S_CX(k), S_CY(k), lb, ub);
                 if (!(lb <= U)) kept &= ~(1u << k);
             }
-#ifndef PF_CU_NOCORNER
-#define PF_CU_NOCORNER 0 /* 1 (experiment, tools/experiments/r06): no corner tests in the publishing pass -- an upper bound of what spreading them over lanes could save */
-#endif
-            if (m > 1 && !PF_CU_NOCORNER) {
+            if (m > 1) {
                 const float ixlo = nextafterf(cxlo, INFINITY), ixhi = nextafterf(cxhi, -INFINITY), iylo = nextafterf(cylo, INFINITY),
                             iyhi = nextafterf(cyhi, -INFINITY);
                 for (int ka = 0; ka < m; ka++) {
@@ -892,7 +881,7 @@ __global__ __launch_bounds__(64) void k_cells_update(pf::KdView tree, CellGeom g
         for (int b4 = 0; b4 < 4; b4++) {
             const uint32_t mask = keep[b4];
             uint32_t kept = mask;
-            if ((mask & (mask - 1u)) && !PF_CU_NOCORNER) { // two or more: squared distances to the sub-cell's four corners, once per candidate
+            if (mask & (mask - 1u)) { // two or more: squared distances to the sub-cell's four corners, once per candidate
                 const float ixlo = nextafterf(bxlo[b4], INFINITY), ixhi = nextafterf(bxhi[b4], -INFINITY), iylo = nextafterf(bylo[b4], INFINITY),
                             iyhi = nextafterf(byhi[b4], -INFINITY);
                 for (uint32_t ra = mask; ra; ra &= ra - 1u) {
@@ -935,7 +924,7 @@ __global__ __launch_bounds__(64) void k_cells_update(pf::KdView tree, CellGeom g
         // every re-cut at the end of the pool, 25 frames spread 144 k live slots over 610 k, and the scan-match kernel, whose waves
         // gather the slots of neighbouring cells, lost 5 % to that (0.388 vs 0.369 ms against the round-3 build on one box).
         const bool in_place = active && total <= old_len;
-        const int alloc = (!active || in_place || total == 0) ? 0 : total + PF_ROW_GROW;
+        const int alloc = (!active || in_place || total == 0) ? 0 : total + PF_ROW_HEADROOM;
         int incl = alloc; // wave prefix sum: one atomic on the pool counter per wave
         for (int off = 1; off < 64; off <<= 1) {
             const int u = __shfl_up(incl, off, 64);
@@ -986,22 +975,14 @@ __global__ __launch_bounds__(64) void k_cells_update(pf::KdView tree, CellGeom g
         // What the four words replace: nothing that counts at a record's first publication (the claim word is PENDING, the others zero: only
         // this record's publications ever write a claimed cell's words), afterwards what the record itself published last -- kept in the
         // record, so the table words are plain stores and the wave does not wait for four exchanges to come back.
-        const int4 last_words = HOIST ? pre_last : (PF_CU_LAST ? *(const int4 *)(rec + PF_REC_LAST) : make_int4(0, 0, 0, 0));
+        const int4 last_words = HOIST ? pre_last : *(const int4 *)(rec + PF_REC_LAST);
         *(int4 *)(rec + PF_REC_LAST) = make_int4((int)word[0], (int)word[1], (int)word[2], (int)word[3]);
-        if (PF_CU_LAST) {
-            if (!(scratch || (rflags & PF_RF_FRESH))) {
-                const int4 last = last_words;
-                unbook((unsigned)last.x); unbook((unsigned)last.y); unbook((unsigned)last.z); unbook((unsigned)last.w);
-            }
-#pragma unroll
-            for (int b4 = 0; b4 < 4; b4++) __hip_atomic_store(&tab[cell + (b4 & 1) + ((b4 & 2) ? PF_CELL_WIN : 0)], word[b4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            unsigned old[4];
-#pragma unroll
-            for (int b4 = 0; b4 < 4; b4++) old[b4] = atomicExch(&tab[cell + (b4 & 1) + ((b4 & 2) ? PF_CELL_WIN : 0)], word[b4]);
-#pragma unroll
-            for (int b4 = 0; b4 < 4; b4++) unbook(old[b4]);
+        if (!(scratch || (rflags & PF_RF_FRESH))) {
+            const int4 last = last_words;
+            unbook((unsigned)last.x); unbook((unsigned)last.y); unbook((unsigned)last.z); unbook((unsigned)last.w);
         }
+#pragma unroll
+        for (int b4 = 0; b4 < 4; b4++) __hip_atomic_store(&tab[cell + (b4 & 1) + ((b4 & 2) ? PF_CELL_WIN : 0)], word[b4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         PF_STAMP(8); // slots + table words
     }
 #ifdef PF_CELLS_PROFILE
@@ -1177,20 +1158,13 @@ __global__ __launch_bounds__(64) void k_score_kd_cells(const float *__restrict__
         }
         return b;
     };
-    // PF_SETPRIO (round-5 experiment, -DPF_SETPRIO=1): a wave that is about to request its table word / row slots is raised over the
-    // waves in their arithmetic, so that the dependent pair of gathers of a beam leaves early.  See tools/experiments/r05/README.md.
-#ifndef PF_SETPRIO
-#define PF_SETPRIO 0
-#endif
     float cwx = 0.0f, cwy = 0.0f;
     unsigned ce = 0u;
     bool cok = j0 < j1 && stage_a(j0, cwx, cwy, ce);
     for (int j = j0; j < j1; j++) {
         float nwx = 0.0f, nwy = 0.0f;
         unsigned ne = 0u;
-        if (PF_SETPRIO) __builtin_amdgcn_s_setprio(2);
         const bool nok = j + 1 < j1 && stage_a(j + 1, nwx, nwy, ne); // in flight while this beam's row is worked on
-        if (PF_SETPRIO == 1) __builtin_amdgcn_s_setprio(0);
         if (cok) {
             const float wx = cwx, wy = cwy;
             const unsigned e = ce;
@@ -1214,7 +1188,6 @@ __global__ __launch_bounds__(64) void k_score_kd_cells(const float *__restrict__
                         cd[q] = pf::kd_load_hot_at(pool_rsrc, base, q * 16);
                         if (CENSUS) pf::census_add(cl.trips, cl.lanes);
                     }
-                if (PF_SETPRIO == 2) __builtin_amdgcn_s_setprio(0); // (variant 2: high from the end point to the row slots' request)
                 float sBest = cell_dist2(cd[0], wx, wy);
                 uint32_t pk = cd[0].z; // node | parent axis << 30 of the best candidate
                 float pcoord = __uint_as_float(cd[0].w);
@@ -1269,8 +1242,7 @@ __global__ __launch_bounds__(64) void k_score_kd_cells(const float *__restrict__
     }
     acc += wpend;
     if (CENSUS) pf::census_flush(cl, census);
-    // out_mode 0: this chunk's partial sum as a float (reduced by the next kernel); 3: as a 16-bit integer; 1: added to the lane's accumulator (integer map weights:
-    // exact in any order; the accumulators are zero on entry and wiped by their reader); 2: nothing (census replay of a pass)
+    // out_mode 0: this chunk's partial sum as a float (reduced by the next kernel); 2: nothing (census replay of a pass)
     if (real && out_mode == 0) out[(size_t)blockIdx.y * n + (direct ? i : slot)] = acc;
     // 3: the partial as a 16-bit integer (integer map weights and beams per chunk x largest |weight| <= 32767: exact) -- half the bytes
     // written here and read back by the reduce kernel (33.6 -> 16.8 MB each way per frame at 100 k particles)
@@ -1279,5 +1251,4 @@ __global__ __launch_bounds__(64) void k_score_kd_cells(const float *__restrict__
     // group's chunks as 16-byte pieces of one contiguous run instead of one strided 2-byte load per chunk (a lane beyond n stores 0)
     // (as non-temporal stores: measured neutral, tools/experiments/r05/README.md)
     if (out_mode == 4) ((short *)out)[((size_t)g * gridDim.y + blockIdx.y) * 64 + threadIdx.x] = real ? (short)(int)acc : (short)0;
-    if (real && out_mode == 1 && acc != 0.0f) unsafeAtomicAdd(&out[slot], acc);
 }

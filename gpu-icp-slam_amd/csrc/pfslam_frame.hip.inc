@@ -7,9 +7,9 @@
 // Round 4 ran that chain through seven kernels, three event records and four event waits (0.18 ms between two 0.38 ms scan-match
 // kernels).  Here it is SIX launches on one stream with no event between them (0.12-0.14 ms):
 //
-//   C (chain)      [gate ORDER]  k_score_kd_cells -> k_reduce_groups -> k_walls<1> (stores REDUCED, spins for ICP; the frame's pose from the
-//                  keys; the scan's wall cells at that pose, sorted) -> k_walls_traverse -> k_walls<3> (new-wall test, KDTree::InsertNode
-//                  for all of them) -> k_cells_update<true> (stores TREE)
+//   C (chain)      [gate ORDER]  k_score_kd_cells -> k_reduce_groups -> k_wall_runs (stores REDUCED, spins for ICP; the frame's pose from
+//                  the keys; the scan's wall cells at that pose, sorted in runs) -> k_walls_rank_traverse -> k_walls<3> (new-wall test,
+//                  KDTree::InsertNode for all of them) -> k_cells_update<true> (stores TREE)
 //   P (particles)  scan upload, k_motion_count -> k_cell_scan -> k_cell_scatter  [wait ev_ftail of the previous frame]  [signal ORDER]  |
 //                  [gate REDUCED]  [wait ev_marked, ev_walked of earlier frames]  k_weights_tiles -> k_scan_apply2 (sums, Neff, header part A)
 //                  -> k_sample_gather
@@ -189,9 +189,9 @@ __global__ __launch_bounds__(256) void k_reduce_groups(const short *__restrict__
 // (kernel.cu:1367-1379), ordered compaction, KDTree::InsertNode for the new walls in list order (k_test_new's rounds).  The weight
 // passes of kernUpdateMapKD are NOT here: the walls' +4 has to follow the free cells' -1 (clamping does not commute), both ride on the
 // free-cell stream (k_free_traverse, k_wall_weights).
-// PART 0: all of it in one launch.  PART 1 / k_walls_traverse / PART 3: the same in three launches -- the wall list (one workgroup), the
-// traversals spread over one wave per compute unit, test + insert (one workgroup): 1081 traversals of ~50 visits each are ISSUE-bound on
-// one compute unit (30 us; a second pass over the very same, now cached, nodes still took 25), not latency-bound.
+// PART 0: all of it in one launch (trees that are not planar).  PART 3: test + insert (one workgroup) behind k_wall_runs and
+// k_walls_rank_traverse, which spread the ranking and the traversals over many compute units: 1081 traversals of ~50 visits each are
+// ISSUE-bound on one compute unit (30 us; a second pass over the very same, now cached, nodes still took 25), not latency-bound.
 template <int PART>
 __global__ __launch_bounds__(1024) void k_walls(const float *__restrict__ scan, const pf::BeamParts *__restrict__ beams, int nb, int sort_n,
                                                PoseSrc src, float *__restrict__ start_out, float *__restrict__ pose_out, long long *__restrict__ stats_next,
@@ -325,14 +325,6 @@ __global__ __launch_bounds__(1024) void k_walls(const float *__restrict__ scan, 
     }
     n = sbase; // <= nb <= cap
     }
-    if (PART == 1) { // the list is handed to the traversal launch
-        for (int i = threadIdx.x; i < n; i += 1024) {
-            const float4 p = cell_to_point(wcell[i], dimx, resx, resy, scalex, scaley, px, py);
-            wall_xy2[i] = make_float2(p.x, p.y);
-        }
-        if (threadIdx.x == 0) wcounts[PF_WC_WALLS] = n;
-        return;
-    }
     // 4. every wall's traversal: nearest index (for the +4 pass and the test) and the link InsertNode would hang it on
     if (PART == 0) {
         for (int i = threadIdx.x; i < n; i += 1024) {
@@ -347,7 +339,7 @@ __global__ __launch_bounds__(1024) void k_walls(const float *__restrict__ scan, 
             lcur[i] = leaf;
             wnew[i] = d > minDist ? 1 : 0; // kernTestCorrespondance: a new wall
         }
-    } else if (keys_s) { // PART 3 behind k_walls_rank_traverse: the walls sit at their ranks, duplicates and beams without a wall are empty places
+    } else { // PART 3 behind k_walls_rank_traverse: the walls sit at their ranks, duplicates and beams without a wall are empty places
         if (threadIdx.x == 0) sbase = 0;
         __syncthreads();
         for (int r0 = 0; r0 < sort_n; r0 += 1024) {
@@ -377,15 +369,6 @@ __global__ __launch_bounds__(1024) void k_walls(const float *__restrict__ scan, 
             __syncthreads();
         }
         n = sbase;
-    } else { // PART 3: k_walls_traverse has left them
-        n = min(wcounts[PF_WC_WALLS], cap);
-        for (int i = threadIdx.x; i < n; i += 1024) {
-            const float2 p = wall_xy2[i];
-            lx[i] = p.x;
-            ly[i] = p.y;
-            lcur[i] = wall_leaf2[i];
-            wnew[i] = wall_new2[i];
-        }
     }
     __syncthreads();
     if (probe && threadIdx.x == 0) probe[PB_WALLS_TRAV - PB_WALLS] = wall_clock64();
@@ -517,13 +500,13 @@ __global__ __launch_bounds__(1024) void k_walls(const float *__restrict__ scan, 
 }
 
 // ---- the wall list over MANY compute units (round 5, second half) --------------------------------------------------------------------
-// k_walls<1> ranks every wall cell among all of them on ONE compute unit: 1088 keys x 17 runs x 7 dependent LDS reads, sixteen waves
+// k_walls<0> ranks every wall cell among all of them on ONE compute unit: 1088 keys x 17 runs x 7 dependent LDS reads, sixteen waves
 // on four SIMDs -- 12 us of instruction issue on the frame's critical chain.  The same work in three pieces:
 //   k_wall_runs           one wave per run of 64 beams: the frame's pose, the beams' wall cells, the wave's own bitonic network; the
 //                         sorted run goes to memory (4 bytes per beam).  Block 0 speaks for the frame (REDUCED, pose, key reset).
 //   k_walls_rank_traverse one wave per run, on a compute unit of its own: all runs into LDS, its 64 keys ranked among all of them (the
-//                         very searches of k_walls<1>: 17 waves side by side instead of in turns), duplicates flagged -- an equal key
-//                         in an earlier run or at an earlier place of its own run: the instance k_walls<1>'s pass would have kept --,
+//                         very searches of k_walls<0>: 17 waves side by side instead of in turns), duplicates flagged -- an equal key
+//                         in an earlier run or at an earlier place of its own run: the instance k_walls<0>'s pass would have kept --,
 //                         and the wall's whole traversal; everything is written at the key's RANK.
 //   k_walls<3>            drops the flagged places while it loads the list (ordered compaction: the x-major unique list of the
 //                         reference's double loop, kernel.cu:1435-1461) and goes on as before.
@@ -600,7 +583,7 @@ __global__ __launch_bounds__(64) void k_walls_rank_traverse(const uint32_t *__re
     if (key == 0xFFFFFFFFu) return; // no wall cell for this beam (the empty keys sort behind every real one: no rank counts them)
     int rank = pos;
     bool dup = pos > 0 && runs[i - 1] == key;
-    for (int r0 = 0; r0 < n_runs; r0 += 4) { // (k_walls<1>'s searches, word for word: four runs side by side)
+    for (int r0 = 0; r0 < n_runs; r0 += 4) { // (k_walls<0>'s searches, word for word: four runs side by side)
         int lo[4] = {0, 0, 0, 0};
         uint32_t pk[4];
         bool on[4];
@@ -633,27 +616,6 @@ __global__ __launch_bounds__(64) void k_walls_rank_traverse(const uint32_t *__re
     c2_s[rank] = b;
     leaf_s[rank] = leaf;
     new_s[rank] = node_dist(tree, b, p) > minDist ? 1 : 0;
-}
-
-// one wave per workgroup: every wall's whole traversal (findCorrespondenceIndexKD, kernel.cu:924-972) + kernTestCorrespondance's flag.
-// (Tried: every lane first requesting the 64 node records the previous frame's traversal of its wall index had visited -- logged
-// there -- so as to walk through warm lines: 25 -> 45 us.  The launch is not waiting for cold lines.)
-template <bool PLANAR>
-__global__ __launch_bounds__(64) void k_walls_traverse(const float2 *__restrict__ wall_xy2, const int *__restrict__ wcounts, int cap, pf::KdView tree,
-                                                       float resx, float resy, int *__restrict__ wall_c2, int *__restrict__ wall_leaf2,
-                                                       int *__restrict__ wall_new2, unsigned long long *__restrict__ probe)
-{
-    pf_stamp(probe);
-    const int i = blockIdx.x * 64 + threadIdx.x, n = min(wcounts[PF_WC_WALLS], cap);
-    if (i >= n) return;
-    const float2 q = wall_xy2[i];
-    const float4 p = make_float4(q.x, q.y, 0.0f, 0.0f);
-    int leaf;
-    const int b = pf::kd_resume<PLANAR, false, true>(tree, p.x, p.y, p.z, INFINITY, 0, 0, nullptr, &leaf);
-    const float cellDiag = pf::fsqrt(resx * resx + resy * resy), minDist = cellDiag / 2.0f;
-    wall_c2[i] = b;
-    wall_leaf2[i] = leaf;
-    wall_new2[i] = node_dist(tree, b, p) > minDist ? 1 : 0;
 }
 
 // ---- F: the free cells' pass of kernUpdateMapKD on the tree as it was before the frame's insert --------------------------------------
@@ -1171,13 +1133,12 @@ static int join_all(pfslam_handle *h)
 // weights, per-phase timing, sharded handles -- takes the round-4 frame; a switch between the two drains the pipeline first)
 static bool frame_v2_ok(pfslam_handle *h, int *chunks_out, int *bpc_out)
 {
-    if (!h->frame_v2 || h->timing >= 2 || h->kd_size <= 0 || !h->integral_w || h->nb > 4096) return false;
+    if (h->timing >= 2 || h->kd_size <= 0 || !h->integral_w || h->nb > 4096) return false;
     if (!org_use_cells(h, nullptr, /*frame_loop=*/true)) return false;
     const int chunks = score_chunks(h);
     const int bpc = (h->nb + chunks - 1) / chunks;
     const int used = (h->nb + bpc - 1) / bpc;
-    static const bool p16_ok = !(ab_env("PFSLAM_P16") && atoi(ab_env("PFSLAM_P16")) == 0);
-    if (!p16_ok || used < 2 || !((float)bpc * h->w_absmax <= 32767.0f)) return false;
+    if (used < 2 || !((float)bpc * h->w_absmax <= 32767.0f)) return false;
     if ((h->gn + PF_SCAN_TILE - 1) / PF_SCAN_TILE > 4096) return false; // k_scan_apply2 / k_sample_gather's LDS prefix maxima (a sharded job scans the GLOBAL weights)
     *chunks_out = used;
     *bpc_out = bpc;
@@ -1306,25 +1267,7 @@ static int fv_cells_passes(pfslam_handle *h, const FvCtx &c)
 static int frame_v2_begin(pfslam_handle *h, int frame, const float *scan_host, int used, int bpc, bool sharded)
 {
     CHK(frame_alloc(h));
-    const bool fresh_cells = !h->cell_tab;
-    if (fresh_cells) { // first use of the cell rows on this handle (launch_score's allocation, verbatim)
-        CHK(dalloc(&h->cell_tab, (size_t)PF_CELL_WIN * PF_CELL_WIN));
-        CHK(dalloc(&h->cell_list, (size_t)PF_CELL_LIST_CAP));
-        HIPCHK(hipMemsetAsync(h->cell_list, 0, (size_t)PF_CELL_LIST_CAP * 4, h->stream));
-        CHK(dalloc(&h->cell_state, PF_CS_ALLOC));
-        HIPCHK(hipMemsetAsync(h->cell_state, 0, PF_CS_ALLOC * 4, h->stream));
-        CHK(dalloc(&h->cell_rec, (size_t)PF_CELL_LIST_CAP * PF_REC_WORDS));
-        HIPCHK(hipMemsetAsync(h->cell_rec, 0, (size_t)PF_CELL_LIST_CAP * PF_REC_WORDS * 4, h->stream));
-        CHK(dalloc(&h->cell_pool, (size_t)PF_CELL_POOL_CAP + PF_ROW_SLACK));
-        CHK(dalloc(&h->cell_touched, (size_t)h->max_wall + 1));
-        HIPCHK(hipMemsetAsync(h->cell_touched, 0, 4, h->stream));
-        CHK(dalloc(&h->fit_acc, (size_t)h->n));
-        HIPCHK(pf_event_create(&h->ev_boxes, hipEventDisableTiming));
-        HIPCHK(pf_event_create(&h->ev_marked, hipEventDisableTiming));
-        HIPCHK(pf_event_create(&h->ev_walked, hipEventDisableTiming));
-        HIPCHK(hipMemsetAsync(h->fit_acc, 0, (size_t)h->n * 4, h->stream));
-        h->cells_wipe_pending = true;
-    }
+    if (!h->cell_tab) CHK(cells_alloc(h));
     const int groups = (h->n + 63) / 64;
     if (!h->group_box) CHK(dalloc(&h->group_box, (size_t)groups));
     if (!h->group_parts) CHK(dalloc(&h->group_parts, (size_t)groups));
@@ -1361,8 +1304,6 @@ static int frame_v2_begin(pfslam_handle *h, int frame, const float *scan_host, i
     const int seq = ++h->seq;
     h->cur_seq = seq;
     h->cur_frame = frame;
-    static const bool scan_gate = !(ab_env("PFSLAM_SCAN_GATE") && atoi(ab_env("PFSLAM_SCAN_GATE")) == 0); // (0: A/B, the ICP solve behind the lane order)
-    static const bool ftail_gate_env = !(ab_env("PFSLAM_FTAIL_GATE") && atoi(ab_env("PFSLAM_FTAIL_GATE")) == 0); // (0: A/B, the free-cell chain's tail as an event)
     h->fv.used = used;
     h->fv.bpc = bpc;
     h->fv.frame = frame;
@@ -1370,7 +1311,7 @@ static int frame_v2_begin(pfslam_handle *h, int frame, const float *scan_host, i
     h->fv.serial = serial;
     h->fv.sharded = sharded;
     h->fv.gates = gates;
-    h->fv.ftail_gate = gates && !serial && scan_gate && ftail_gate_env;
+    h->fv.ftail_gate = gates && !serial;
     h->x_frame = h->x; h->y_frame = h->y; h->th_frame = h->th; // this frame's pose block (swap_pose_blocks moves h->x .. on before the cells' passes are enqueued)
     const FvCtx c = fv_ctx(h);
     hipStream_t P = c.P, F = c.F;
@@ -1382,7 +1323,6 @@ static int frame_v2_begin(pfslam_handle *h, int frame, const float *scan_host, i
     {
         const int bits = h->n <= 400000 ? 6 : PF_CELL_BITS_MAX, ncell = 1 << (3 * bits);
         int *hist = h->cells, *cursor = h->cells + ncell, *tile_tot = h->cells + 2 * ncell;
-        static const float theta_weight = ab_env("PFSLAM_THETA_WEIGHT") ? (float)atof(ab_env("PFSLAM_THETA_WEIGHT")) : 1.0f;
         float *cloud_in = h->cloud + 4 * (c.s2 ^ 1), *cloud_out = h->cloud + 4 * c.s2;
         { // the frame's scan: every reader on the other streams takes it with the lane order (ev_order)
             float *hs = h->h_scan + (size_t)(seq % PF_HDR_SLOTS) * h->nb;
@@ -1397,9 +1337,9 @@ static int frame_v2_begin(pfslam_handle *h, int frame, const float *scan_host, i
             // (gates) the scan is there: all the ICP solve waits for -- it then starts behind the previous frame's wall weights instead of behind
             // this frame's lane order, which matters when the scan-match kernel is too short to hide it (1000 particles: the wall kernel
             // waited for the increment)
-            if (gates && !serial && scan_gate) hipLaunchKernelGGL(k_signal, dim3(1), dim3(64), 0, P, fl + PF_FL_SCAN, seq);
+            if (gates && !serial) hipLaunchKernelGGL(k_signal, dim3(1), dim3(64), 0, P, fl + PF_FL_SCAN, seq);
         }
-        const float reach = h->scan_reach * theta_weight;
+        const float reach = h->scan_reach;
         h->tparts_cur = nullptr;
         if (!h->cloud_valid) {
             hipLaunchKernelGGL(k_cloud_seed, dim3(1), dim3(256), 0, P, (const float *)h->x, (const float *)h->y, (const float *)h->th, h->n, reach, cloud_in, c.sig);
@@ -1436,8 +1376,7 @@ static int frame_v2_begin(pfslam_handle *h, int frame, const float *scan_host, i
         if (ftail_gate) { // the gate for the scan, announcing first that the previous frame's free-cell chain (k_wall_weights) is over
             hipLaunchKernelGGL(k_gate_signal, dim3(1), dim3(64), 0, F, fl + PF_FL_FTAIL, seq - 1, (const int *)(fl + PF_FL_SCAN), seq, h->gate_err_dev);
             HIPCHK(hipGetLastError());
-        } else if (gates && !serial && scan_gate) FV_EDGE_WAIT(F, PF_FL_SCAN, h->ev_order, 0);
-        else FV_EDGE_WAIT(F, PF_FL_ORDER, h->ev_order, 0);
+        } else FV_EDGE_WAIT(F, PF_FL_ORDER, h->ev_order, 0);
         if (h->shift_pending) HIPCHK(hipStreamWaitEvent(F, h->ev_shift, 0)); // (the solve starts from the shifted pose)
         h->shift_pending = false;
         const dim3 gi((h->nb + 1023) / 1024);
@@ -1503,8 +1442,7 @@ static int frame_v2_score(pfslam_handle *h)
         hipLaunchKernelGGL((k_reduce_groups<4>), dim3(groups), dim3(256), 0, C, (const short *)h->pgroup, h->n, groups, used, (const int *)c.order, h->fit, c.stats,
                            PB(PB_REDUCE), h->goff);
     else {
-        static const int reduce_wgs = ab_env("PFSLAM_REDUCE_WGS") ? std::max(1, atoi(ab_env("PFSLAM_REDUCE_WGS"))) : PF_REDUCE_WGS;
-        hipLaunchKernelGGL((k_reduce_groups<1>), dim3(std::min((groups + 3) / 4, reduce_wgs)), dim3(256), 0, C, (const short *)h->pgroup, h->n, groups, used,
+        hipLaunchKernelGGL((k_reduce_groups<1>), dim3(std::min((groups + 3) / 4, PF_REDUCE_WGS)), dim3(256), 0, C, (const short *)h->pgroup, h->n, groups, used,
                            (const int *)c.order, h->fit, c.stats, PB(PB_REDUCE), h->goff);
     }
     HIPCHK(hipGetLastError());
@@ -1529,46 +1467,33 @@ static int frame_v2_chain(pfslam_handle *h)
         const size_t lds = (size_t)sort_n * 9 * sizeof(uint32_t);
         if (!h->walls_attr_set) {
             HIPCHK(hipFuncSetAttribute((const void *)k_walls<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIPCHK(hipFuncSetAttribute((const void *)k_walls<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             HIPCHK(hipFuncSetAttribute((const void *)k_walls<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             h->walls_attr_set = true;
         }
         const int cx = (int)roundf(0.5f * h->dimx + h->cfg.map_res_x / 2), cy = (int)roundf(0.5f * h->dimy + h->cfg.map_res_y / 2);
         const int wait_poseg = c.multi ? 1 : 0;
-        static const bool walls_one = ab_env("PFSLAM_WALLS_ONE") && atoi(ab_env("PFSLAM_WALLS_ONE")) != 0; // A/B: the whole wall chain in one launch
 #define PF_WALLS_ARGS dim3(1), dim3(1024), lds, C, (const float *)h->scan, (const pf::BeamParts *)h->beam_angle, h->nb, sort_n, c.psrc, h->start, h->pose, c.stats_next, \
                       cx, cy, h->dimx, h->dimy, h->cfg.map_res_x, h->cfg.map_res_y, h->cfg.map_scale_x, h->cfg.map_scale_y, c.tv, h->hot, h->parent, h->kz, h->kw,   \
                       h->kd_state, h->kd_cap, sort_n, h->wall_c2, h->wcounts, h->fs + PF_FS_BOUND + ((seq + 1) & 3), (const int *)h->cell_state, h->cell_touched
-        if (walls_one || h->planar == 0) {
+        if (h->planar == 0) {
             hipLaunchKernelGGL(k_walls<0>, PF_WALLS_ARGS, PB(PB_WALLS), h->wall_xy2, h->wall_leaf2, h->wall_new2, gates ? fl : (int *)nullptr, seq, h->gate_err_dev,
                                (const uint32_t *)nullptr, (const int *)nullptr, wait_poseg, h->trig);
         } else {
-            static const bool walls_rank = !(ab_env("PFSLAM_WALLS_RANK") && atoi(ab_env("PFSLAM_WALLS_RANK")) == 0); // 0 (A/B): the ranking on one compute unit (k_walls<1>)
-            if (walls_rank) {
-                hipLaunchKernelGGL(k_wall_runs, dim3(sort_n / 64), dim3(64), 0, C, (const float *)h->scan, (const pf::BeamParts *)h->beam_angle, h->nb, c.psrc, h->start, h->pose,
-                                   c.stats_next, cx, cy, h->dimx, h->dimy, h->cfg.map_res_x, h->cfg.map_res_y, h->wall_runs, h->wall_keys_s, PB(PB_WALLS),
-                                   gates ? fl : (int *)nullptr, seq, h->gate_err_dev, wait_poseg, h->trig);
-                // (4 workgroups per run of 64 keys: ranks + traversals 34.4 -> 32.4 us, frame -2.5 us at 1000 and at 100 000 particles)
-                const int walls_split = 4;
-                hipLaunchKernelGGL(k_walls_rank_traverse<true>, dim3(sort_n / 64 * walls_split), dim3(64), (size_t)sort_n * 4, C, (const uint32_t *)h->wall_runs, sort_n,
-                                   (const float *)h->pose, h->dimx, h->cfg.map_res_x, h->cfg.map_res_y, h->cfg.map_scale_x, h->cfg.map_scale_y, c.tv, h->wall_keys_s,
-                                   h->wall_xy2, h->wall_c2s, h->wall_leaf2, h->wall_new2, PB(PB_WALLS_REP), walls_split);
-                hipLaunchKernelGGL(k_walls<3>, PF_WALLS_ARGS, PB(PB_WALLS), h->wall_xy2, h->wall_leaf2, h->wall_new2, (int *)nullptr, seq, (int *)nullptr,
-                                   (const uint32_t *)h->wall_keys_s, (const int *)h->wall_c2s);
-            } else {
-                hipLaunchKernelGGL(k_walls<1>, PF_WALLS_ARGS, PB(PB_WALLS), h->wall_xy2, h->wall_leaf2, h->wall_new2, gates ? fl : (int *)nullptr, seq, h->gate_err_dev,
-                                   (const uint32_t *)nullptr, (const int *)nullptr, wait_poseg, h->trig);
-                hipLaunchKernelGGL(k_walls_traverse<true>, dim3(sort_n / 64), dim3(64), 0, C, (const float2 *)h->wall_xy2, (const int *)h->wcounts, sort_n, c.tv,
-                                   h->cfg.map_res_x, h->cfg.map_res_y, h->wall_c2, h->wall_leaf2, h->wall_new2, PB(PB_WALLS_REP));
-                hipLaunchKernelGGL(k_walls<3>, PF_WALLS_ARGS, PB(PB_WALLS), h->wall_xy2, h->wall_leaf2, h->wall_new2, (int *)nullptr, seq, (int *)nullptr);
-            }
+            hipLaunchKernelGGL(k_wall_runs, dim3(sort_n / 64), dim3(64), 0, C, (const float *)h->scan, (const pf::BeamParts *)h->beam_angle, h->nb, c.psrc, h->start, h->pose,
+                               c.stats_next, cx, cy, h->dimx, h->dimy, h->cfg.map_res_x, h->cfg.map_res_y, h->wall_runs, h->wall_keys_s, PB(PB_WALLS),
+                               gates ? fl : (int *)nullptr, seq, h->gate_err_dev, wait_poseg, h->trig);
+            // (4 workgroups per run of 64 keys: ranks + traversals 34.4 -> 32.4 us, frame -2.5 us at 1000 and at 100 000 particles)
+            const int walls_split = 4;
+            hipLaunchKernelGGL(k_walls_rank_traverse<true>, dim3(sort_n / 64 * walls_split), dim3(64), (size_t)sort_n * 4, C, (const uint32_t *)h->wall_runs, sort_n,
+                               (const float *)h->pose, h->dimx, h->cfg.map_res_x, h->cfg.map_res_y, h->cfg.map_scale_x, h->cfg.map_scale_y, c.tv, h->wall_keys_s,
+                               h->wall_xy2, h->wall_c2s, h->wall_leaf2, h->wall_new2, PB(PB_WALLS_REP), walls_split);
+            hipLaunchKernelGGL(k_walls<3>, PF_WALLS_ARGS, PB(PB_WALLS), h->wall_xy2, h->wall_leaf2, h->wall_new2, (int *)nullptr, seq, (int *)nullptr,
+                               (const uint32_t *)h->wall_keys_s, (const int *)h->wall_c2s);
         }
 #undef PF_WALLS_ARGS
         HIPCHK(hipGetLastError());
         if (!gates) HIPCHK(hipEventRecord(h->ev_tree2, C)); // (gates: k_cells_update says so in front of its own work)
-        // (16: tools/experiments/r05/recut_ab.sh -- half as many ~100 us compaction passes as with 8, the pool not yet spread enough for the scan-match kernel to notice)
-        static const int recut_every = ab_env("PFSLAM_CELLS_RECUT_EVERY") ? atoi(ab_env("PFSLAM_CELLS_RECUT_EVERY")) : 16;
-        const int recut = recut_every > 0 && h->cells_passes > 0 && h->cells_passes % recut_every == 0 ? 1 : 0;
+        const int recut = h->cells_passes > 0 && h->cells_passes % PF_CELLS_RECUT_EVERY == 0 ? 1 : 0;
         if (recut) HIPCHK(hipMemsetAsync(h->cell_state + PF_CS_POOL, 0, 4, C));
         // the records a walk pass finished `lag` frames ago (the particle chain waited for it a frame ago); synchronous frame: everything (the walked words say so)
         hipLaunchKernelGGL(k_cells_update<true>, dim3(PF_CELLS_GRID), dim3(64), 0, C, c.tv, c.geo, h->cell_tab, (const int *)h->cell_list, h->cell_state, h->cell_pool,

@@ -40,14 +40,8 @@ enum { PF_T_SCORE = 0, PF_T_MOTION, PF_T_MEASURE, PF_T_MAP, PF_T_RESAMPLE, PF_T_
 
 // Environment switches.  What the library reads with getenv() is the documented set (tools/README.md): test switches (one-stream mode,
 // events instead of gates, fault injection, canonical lane order, capacities of the overflow tests, the variant, the host build's threads).
-// The A/B knobs of past experiments (tools/experiments/*: priorities, workgroup counts, chains kept for comparison) go through ab_env()
-// and exist only in a -DPF_EXPERIMENTS build (PFSLAM_EXTRA_FLAGS=-DPF_EXPERIMENTS python gpu-icp-slam_amd/build.py): the product takes
-// the defaults they lost their A/B to, and the branches behind them fold away.
-#ifdef PF_EXPERIMENTS
-static inline const char *ab_env(const char *name) { return getenv(name); }
-#else
-static inline const char *ab_env(const char *) { return nullptr; }
-#endif
+// An A/B experiment is built as a source variant (PFSLAM_EXTRA_FLAGS + PFSLAM_LIB, or a patch under tools/experiments/), not kept as a
+// switch in the product.
 
 // How long a stream gate (pfslam_frame.hip.inc) spins before it gives up, in ticks of the 100 MHz wall clock: 1 s for a handle on its own
 // (nothing it waits for takes a millisecond); 60 s once the process holds a shard of a multi-GPU job -- there a gate may sit behind a
@@ -186,7 +180,7 @@ struct pfslam_handle {
     bool gates_ok = false;          // ... and they make progress independently of one another
     bool gates_live = false;        // the frames in flight use gates (a change of mode drains the pipeline first)
     hipEvent_t ev_poseg = nullptr;  // events mode, sharded: the gathered pose blocks are there (P -> C)
-    int lag = 1; // frames the host may run ahead (PFSLAM_LAG; 0 = every step settles itself)
+    int lag = 1; // frames the host may run ahead (pfslam_set_lag; 0 = every step settles itself)
     float scan_reach = 8.0f; // mean in-range beam length of the current scan (m): the lever arm of a heading difference
     std::vector<pfslam_particle> h_particles;
     std::vector<float> h_tmp;
@@ -268,17 +262,15 @@ struct pfslam_handle {
     bool update_unsnapped = false; // the last post-insert k_cells_update read the raw list counter: the next marking pass starts behind it
     bool cells_snap = false;       // this frame's k_cells_update<true> may run beside the next frame's marking pass: records below the walk pass's snapshot only
     pf::BeamParts *beam_angle = nullptr; // LIDAR_ANGLE(j) and its cos / sin as doubles, nb entries
-    float *fit_acc = nullptr;    // per-lane score accumulators of the cell-row kernel (zero between passes)
     // ---- round-5 frame loop (pfslam_frame.hip.inc): four in-order chains, a fixed set of events between them ----
     int trig = 0;                 // pfslam_set_trig: 1 = the device library's cosf / sinf / erfcinvf instead of the pf_math.h specification (see sincos_sum_spec)
     int serial = 0;               // PFSLAM_SERIAL=1: every frame's launches on ONE stream, in enqueue order (same results, same bookkeeping)
-    int frame_v2 = 1;             // PFSLAM_FRAME_V2=0: the round-4 frame (A/B runs)
     bool pipe_live = false;       // the last frame was a round-5 frame: its events and ring slots are what the next one waits on
     bool cloud_valid = false;     // the cloud statistics k_motion_count starts from describe the current particles
     int publish_lag = 2;          // a publishing pass takes the records walked `publish_lag` frames ago (ordered through ev_join)
     int *fs = nullptr;            // frame state words (PF_FS_*)
     int *wcounts = nullptr;       // k_walls: wall cells, new walls, header flags, map size
-    float2 *wall_xy2 = nullptr;   // k_walls<1> -> k_walls_traverse -> k_walls<3>: the frame's wall points, the link each falls off, new-wall flags
+    float2 *wall_xy2 = nullptr;   // k_walls_rank_traverse -> k_walls<3>: the frame's wall points, the link each falls off, new-wall flags
     int *wall_leaf2 = nullptr, *wall_new2 = nullptr;
     int *wall_c2 = nullptr;       // nearest index of every wall of the frame (k_walls -> k_wall_weights)
     uint32_t *wall_runs = nullptr, *wall_keys_s = nullptr; // k_wall_runs -> k_walls_rank_traverse -> k_walls<3>: the beams' wall cells sorted inside runs of 64; in
@@ -831,9 +823,8 @@ extern "C" void pfslam_default_config(pfslam_config *cfg)
 // caches (14 us between two 6 us kernels of the frame's critical chain): a device-scope release is what these events need.
 static hipError_t pf_event_create(hipEvent_t *e, unsigned flags)
 {
-    static const bool dev_scope = !(ab_env("PFSLAM_EVENT_SYSTEM") && atoi(ab_env("PFSLAM_EVENT_SYSTEM")) != 0); // A/B: 1 = the default (system) release
-    hipError_t rc = hipEventCreateWithFlags(e, flags | (dev_scope ? hipEventReleaseToDevice : 0u));
-    if (rc != hipSuccess && dev_scope) { // (a runtime that does not know the flag)
+    hipError_t rc = hipEventCreateWithFlags(e, flags | hipEventReleaseToDevice);
+    if (rc != hipSuccess) { // (a runtime that does not know the flag)
         (void)hipGetLastError();
         rc = hipEventCreateWithFlags(e, flags);
     }
@@ -885,17 +876,13 @@ static int create_impl(pfslam_handle *h)
         // priority their workgroups queue behind that flood (the one-workgroup ICP solve: 33 -> 284 us)
         int lo = 0, hi = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        static const bool prio = !(ab_env("PFSLAM_AUX_PRIO") && atoi(ab_env("PFSLAM_AUX_PRIO")) == 0);
-        HIPCHK(hipStreamCreateWithPriority(&h->aux, hipStreamNonBlocking, prio ? hi : lo));
-        static const int kprio = ab_env("PFSLAM_K_PRIO") ? atoi(ab_env("PFSLAM_K_PRIO")) : 1; // 0 low, 1 normal (default), 2 high
-        HIPCHK(hipStreamCreateWithPriority(&h->cstream, hipStreamNonBlocking, kprio == 2 ? hi : kprio == 1 ? (lo + hi) / 2 : lo)); // (beside the scan-match kernel: it must not get in its way)
-        static const int fprio = ab_env("PFSLAM_F_PRIO") ? atoi(ab_env("PFSLAM_F_PRIO")) : 2; // A/B: the free cells' stream 0 low, 1 normal, 2 high
-        HIPCHK(hipStreamCreateWithPriority(&h->istream, hipStreamNonBlocking, !prio ? lo : fprio == 2 ? hi : fprio == 1 ? (lo + hi) / 2 : lo));
+        HIPCHK(hipStreamCreateWithPriority(&h->aux, hipStreamNonBlocking, hi));
+        HIPCHK(hipStreamCreateWithPriority(&h->cstream, hipStreamNonBlocking, (lo + hi) / 2)); // (beside the scan-match kernel: it must not get in its way)
+        HIPCHK(hipStreamCreateWithPriority(&h->istream, hipStreamNonBlocking, hi)); // (the free cells' stream)
         HIPCHK(pf_event_create(&h->ev_tree, hipEventDisableTiming));
         HIPCHK(pf_event_create(&h->ev_scored, hipEventDisableTiming));
         h->fstream = h->istream; // round-5 frames: the free cells' chain (their ICP solve rides on the cells' stream)
         if (const char *e = getenv("PFSLAM_SERIAL")) h->serial = atoi(e) != 0;
-        if (const char *e = ab_env("PFSLAM_FRAME_V2")) h->frame_v2 = atoi(e) != 0;
         if (const char *e = getenv("PFSLAM_GATES")) h->gates = atoi(e) != 0;
         if (const char *e = getenv("PFSLAM_FAULT")) h->fault = atoi(e);
         if (const char *e = getenv("PFSLAM_STABLE_ORDER")) h->stable_order = atoi(e) != 0;
@@ -972,7 +959,6 @@ static int create_impl(pfslam_handle *h)
         h->hdr_dev = (HostHeader *)dp;
     }
     HIPCHK(hipHostMalloc((void **)&h->h_scan, (size_t)PF_HDR_SLOTS * h->nb * 4));
-    if (const char *e = ab_env("PFSLAM_LAG")) h->lag = std::min(std::max(atoi(e), 0), PF_MAX_LAG);
     if (const char *e = getenv("PFSLAM_VARIANT")) h->variant = atoi(e); // initial pfslam_set_variant (A/B runs, the fuzz)
     h->h_nodes.reserve(1024);
     // particleFilterInit (kernel.cu:122-132): grid = -100, particles at the origin with w = 1, robotPos = 0
@@ -1079,7 +1065,6 @@ extern "C" int pfslam_destroy(pfslam_handle *h)
     if (h->ev_boxes) (void)hipEventDestroy(h->ev_boxes);
     if (h->ev_marked) (void)hipEventDestroy(h->ev_marked);
     if (h->beam_angle) (void)hipFree(h->beam_angle);
-    if (h->fit_acc) (void)hipFree(h->fit_acc);
     frame_free(h);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1563,8 +1548,7 @@ static int score_chunks(const pfslam_handle *h)
     // Below ~40 k particles fewer, longer waves win (a wave's prologue and the launch's ramp against the beams it scores): ~160 chunks per
     // group between 24 576 and 65 536 waves (profiles/r05_sweep_waves.txt: 10 k particles 0.218 -> 0.209 ms per frame, 20 k 0.2493 -> 0.2478,
     // 1 k / 4 k unchanged within noise)
-    static const int target_env = ab_env("PFSLAM_TARGET_WAVES") ? atoi(ab_env("PFSLAM_TARGET_WAVES")) : 0;
-    const int target = target_env > 0 ? target_env : std::max(24576, std::min(65536, groups * 160));
+    const int target = std::max(24576, std::min(65536, groups * 160));
     int chunks = (target + groups - 1) / groups;
     chunks = std::max(1, std::min(chunks, h->nb)); // small particle counts go down to one beam per wave
     // Beam-chunk partials added afterwards equal the reference's sequential beam-order float sum only when every term is an
@@ -1580,6 +1564,9 @@ static int score_chunks(const pfslam_handle *h)
                                  stream, cost that kernel anything between 0 and 80 us from run to run */
 #define PF_CELLS_GRID 512 /* workgroups (one wave each) of k_cells_update, grid-stride over the records: two fit a CU (78 KB of LDS each), so 512
                              are resident together -- 2048 of them queued through the few free places while the first 476 worked (56 us) */
+#define PF_CELLS_RECUT_EVERY 16 /* publishing updates between two re-cuts of every cell's rows (launch_cells_update, the round-5 frame; tools/experiments/r05/recut_ab.sh:
+                                   half as many ~100 us compaction passes as with 8, the pool not yet spread enough for the scan-match kernel to notice) */
+#define PF_CELLS_BOX_MAX 24.0f /* widest beam-end box of a wave, in lattice cells per side, that still takes the cell rows (org_use_cells) */
 struct CellArgs { unsigned *tab; int *list, *cs; uint4 *pool; int *rec; };
 __global__ void k_cells_reset(int *cs, int list_cap, int pool_cap)
 {
@@ -1613,8 +1600,7 @@ static int launch_cells_update(pfslam_handle *h, hipStream_t st)
     // move to the pool's end, and after ~20 frames the rows a wave gathers together no longer sit together -- the scan-match kernel,
     // with nothing running beside it, went from 0.37 to 0.40-0.42 ms between the 10th and the 20th frame after a wipe (the round-3
     // build, which cut everything every frame, stayed flat).  A cut needs no walk: the records hold the candidates.
-    static const int recut_every = ab_env("PFSLAM_CELLS_RECUT_EVERY") ? atoi(ab_env("PFSLAM_CELLS_RECUT_EVERY")) : 16; // (as in the round-5 frame: tools/experiments/r05/recut_ab.sh)
-    const int recut = recut_every > 0 && h->cells_passes > 0 && h->cells_passes % recut_every == 0 ? 1 : 0;
+    const int recut = h->cells_passes > 0 && h->cells_passes % PF_CELLS_RECUT_EVERY == 0 ? 1 : 0;
     if (recut) HIPCHK(hipMemsetAsync(h->cell_state + PF_CS_POOL, 0, 4, st));
     hipLaunchKernelGGL(k_cells_update<true>, dim3(PF_CELLS_GRID), dim3(64), 0, st, kd_view(h), geo, h->cell_tab, (const int *)h->cell_list, h->cell_state,
                        h->cell_pool, h->cell_rec, h->cells_gen, (const int *)h->cell_touched, (int)(h->cells_passes & 15), recut, h->cells_snap ? 1 : 0);
@@ -1645,18 +1631,37 @@ static bool org_use_cells(const pfslam_handle *h, bool *use_plan, bool frame_loo
     const bool organised = h->planar && h->variant != 2 && h->variant != 1 && h->n > 64 && (h->n >= plan_min_n || h->variant >= 3);
     const float Dside = h->n <= 400000 ? 64.0f : 128.0f;
     const float box_cells = 2.0f * (6.4f * h->cloud_sigma / Dside) * cbrtf(64.0f * Dside * Dside * Dside / (float)h->n) / std::min(h->cfg.map_res_x, h->cfg.map_res_y);
-    static const float box_max = ab_env("PFSLAM_CELLS_BOX_MAX") ? (float)atof(ab_env("PFSLAM_CELLS_BOX_MAX")) : 24.0f;
-    const bool narrow = h->variant == 3 || !(box_cells > box_max);
+    const bool narrow = h->variant == 3 || !(box_cells > PF_CELLS_BOX_MAX);
     const bool use_cells = organised && h->lattice_ok && h->variant != 4 && !h->cells_suspended && narrow; // lattice-cell rows (kd_cells.hip.inc)
     if (use_plan) *use_plan = !use_cells && h->planar && h->variant != 2 && (h->n >= plan_min_n || h->variant >= 3);
     return use_cells;
 }
-__global__ void k_reduce_partials_minmax(float *partial, int n, int chunks, const int *order, float *fit, int goff, long long *stats,
-                                         const float *x, const float *y, const float *th, int wipe, int p16);
+__global__ void k_reduce_partials_minmax(const float *partial, int n, int chunks, const int *order, float *fit, int goff, long long *stats,
+                                         const float *x, const float *y, const float *th, int p16);
 __global__ void k_reduce_partials_minmax_wide(const float *partial, int n, int chunks, const int *order, float *fit, long long *stats);
 template <typename T> __global__ void k_minmax(const T *fit, int n, int goff, long long *stats);
 static int join_icp(pfslam_handle *h);
 static int launch_stats_reset(pfslam_handle *h, hipStream_t st);
+
+// first use of the cell rows on this handle (launch_score, the round-5 frame): the rows start wiped
+static int cells_alloc(pfslam_handle *h)
+{
+    CHK(dalloc(&h->cell_tab, (size_t)PF_CELL_WIN * PF_CELL_WIN));
+    CHK(dalloc(&h->cell_list, (size_t)PF_CELL_LIST_CAP));
+    HIPCHK(hipMemsetAsync(h->cell_list, 0, (size_t)PF_CELL_LIST_CAP * 4, h->stream));
+    CHK(dalloc(&h->cell_state, PF_CS_ALLOC)); // ([64, 128): PF_CELLS_PROFILE builds)
+    HIPCHK(hipMemsetAsync(h->cell_state, 0, PF_CS_ALLOC * 4, h->stream));
+    CHK(dalloc(&h->cell_rec, (size_t)PF_CELL_LIST_CAP * PF_REC_WORDS));
+    HIPCHK(hipMemsetAsync(h->cell_rec, 0, (size_t)PF_CELL_LIST_CAP * PF_REC_WORDS * 4, h->stream)); // generation 0: no record is written
+    CHK(dalloc(&h->cell_pool, (size_t)PF_CELL_POOL_CAP + PF_ROW_SLACK));
+    CHK(dalloc(&h->cell_touched, (size_t)h->max_wall + 1));
+    HIPCHK(hipMemsetAsync(h->cell_touched, 0, 4, h->stream));
+    HIPCHK(pf_event_create(&h->ev_boxes, hipEventDisableTiming));
+    HIPCHK(pf_event_create(&h->ev_marked, hipEventDisableTiming));
+    HIPCHK(pf_event_create(&h->ev_walked, hipEventDisableTiming));
+    h->cells_wipe_pending = true;
+    return 0;
+}
 
 // fuse_minmax: the frame loops want the packed min/max keys of this shard right away; the reduce kernel then produces them
 // too (one launch less on the chain).  Needs more than one beam chunk, which every launch below ~8 M particles has.
@@ -1692,57 +1697,31 @@ static int launch_score(pfslam_handle *h, bool fuse_minmax = false, pf::KdCensus
     // for the plan); at 1 m they took 60 ms against 2.7 (tools/sigma_sweep.py, profiles/r04_sigma_sweep.json).  variant 3 forces them.
     const bool use_cells = use_cells_, use_plan = use_plan_; // (org_use_cells: lattice-cell rows, else the round-2 plan, else the plain traversal)
     const CellGeom geo{h->cfg.map_res_x, h->cfg.map_res_y, 1.0f / h->cfg.map_res_x, 1.0f / h->cfg.map_res_y};
-    if (use_cells && !h->cell_tab) {
-        CHK(dalloc(&h->cell_tab, (size_t)PF_CELL_WIN * PF_CELL_WIN));
-        CHK(dalloc(&h->cell_list, (size_t)PF_CELL_LIST_CAP));
-        HIPCHK(hipMemsetAsync(h->cell_list, 0, (size_t)PF_CELL_LIST_CAP * 4, h->stream));
-        CHK(dalloc(&h->cell_state, PF_CS_ALLOC)); // ([64, 128): PF_CELLS_PROFILE builds)
-        HIPCHK(hipMemsetAsync(h->cell_state, 0, PF_CS_ALLOC * 4, h->stream));
-        CHK(dalloc(&h->cell_rec, (size_t)PF_CELL_LIST_CAP * PF_REC_WORDS));
-        HIPCHK(hipMemsetAsync(h->cell_rec, 0, (size_t)PF_CELL_LIST_CAP * PF_REC_WORDS * 4, h->stream)); // generation 0: no record is written
-        CHK(dalloc(&h->cell_pool, (size_t)PF_CELL_POOL_CAP + PF_ROW_SLACK));
-        CHK(dalloc(&h->cell_touched, (size_t)h->max_wall + 1));
-        HIPCHK(hipMemsetAsync(h->cell_touched, 0, 4, h->stream));
-        CHK(dalloc(&h->fit_acc, (size_t)h->n));
-        HIPCHK(pf_event_create(&h->ev_boxes, hipEventDisableTiming));
-        HIPCHK(pf_event_create(&h->ev_marked, hipEventDisableTiming));
-        HIPCHK(pf_event_create(&h->ev_walked, hipEventDisableTiming));
-        HIPCHK(hipMemsetAsync(h->fit_acc, 0, (size_t)h->n * 4, h->stream));
-        h->cells_wipe_pending = true;
-    }
+    if (use_cells && !h->cell_tab) CHK(cells_alloc(h));
     // The rows persist (kd_cells.hip.inc).  Synchronous pass: new cells are marked, walked and published in front of the scan-match
     // kernel, on this stream (stage-level calls, the first pass after a wipe, per-phase timing).  Asynchronous pass (frame loops):
     // marking and the walk of the new cells run on the aux stream UNDER the scan-match kernel, whose lanes take the generic traversal
     // in a cell that has no rows yet; k_cells_update publishes them behind the frame's insert (launch_map_update_device).
-    static const int cells_mode = ab_env("PFSLAM_CELLS_MODE") ? atoi(ab_env("PFSLAM_CELLS_MODE")) : 0; // 1: always synchronous (A/B)
-    const bool cells_sync = use_cells && (!h->cells_async || h->cells_wipe_pending || census != nullptr || cells_mode == 1);
+    const bool cells_sync = use_cells && (!h->cells_async || h->cells_wipe_pending || census != nullptr);
     if (use_cells && h->cells_wipe_pending) {
         CHK(join_map(h)); // the previous frame's k_cells_update is the table's last writer
         CHK(cells_wipe(h));
     }
     // default: counting sort over Hilbert cells of the cloud (3 launches), 2^18 cells up to 400 k particles, 2^21 above
-    static const float theta_weight = ab_env("PFSLAM_THETA_WEIGHT") ? (float)atof(ab_env("PFSLAM_THETA_WEIGHT")) : 1.0f;
     if (h->variant != 1 && h->n > 64) {
         const int bits = h->n <= 400000 ? 6 : PF_CELL_BITS_MAX, ncell = 1 << (3 * bits);
         int *hist = h->cells, *cursor = h->cells + ncell, *tile_tot = h->cells + 2 * ncell;
-        hipLaunchKernelGGL(k_cell_count, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, h->x, h->y, h->th, h->n, h->scan_reach * theta_weight, bits, h->mkey, hist,
+        hipLaunchKernelGGL(k_cell_count, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, h->x, h->y, h->th, h->n, h->scan_reach, bits, h->mkey, hist,
                            use_cells ? h->cell_state : (int *)nullptr, geo, h->d_sigma);
         hipLaunchKernelGGL(k_cell_scan, dim3(ncell / 1024), dim3(256), 0, h->stream, hist, cursor, tile_tot);
         hipLaunchKernelGGL(k_cell_scatter, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, h->mkey, h->n, cursor, tile_tot, ncell / 1024, h->order2);
         HIPCHK(hipGetLastError());
         order = h->order2;
     } // variant 1 = identity lane order
-    // cell-row kernel on a map with integer weights, several beam chunks, frame loop: the chunks ADD their sums to one accumulator
-    // per lane (exact in any order) instead of writing `used` partials per lane for the reduce kernel to read back (33 MB per frame)
-    // MEASURED AND OFF BY DEFAULT (PFSLAM_ACC_OUT=1 turns it on): the reduce kernel gets 10 us shorter and 33 MB of writes go away, but
-    // 8.4 M float atomics cost the scan-match kernel 30 us (0.626 -> 0.656 ms) -- plain stores retire for free next to VALU-bound work
-    static const bool acc_enabled = ab_env("PFSLAM_ACC_OUT") && atoi(ab_env("PFSLAM_ACC_OUT")) != 0;
-    const bool acc_out = acc_enabled && use_cells && h->integral_w && used > 1 && fuse_minmax && !census;
     const int direct = used > 1 ? 0 : 1;
     // beam-chunk partials of the cell-row kernel as 16-bit integers: integer weights, and a chunk's sum cannot leave the range
-    const bool wide_reduce = used >= 256 && fuse_minmax && !sharded && h->goff == 0 && !acc_out;
-    static const bool p16_ok = !(ab_env("PFSLAM_P16") && atoi(ab_env("PFSLAM_P16")) == 0);
-    const bool p16 = p16_ok && use_cells && h->integral_w && used > 1 && fuse_minmax && !acc_out && !wide_reduce && (float)bpc * h->w_absmax <= 32767.0f;
+    const bool wide_reduce = used >= 256 && fuse_minmax && !sharded && h->goff == 0;
+    const bool p16 = use_cells && h->integral_w && used > 1 && fuse_minmax && !wide_reduce && (float)bpc * h->w_absmax <= 32767.0f;
     h->plan_valid = use_plan;
     h->cells_valid = use_cells;
     if (use_plan || use_cells) { // the pose boxes do not need the map: in front of the join
@@ -1810,8 +1789,7 @@ static int launch_score(pfslam_handle *h, bool fuse_minmax = false, pf::KdCensus
     // (an event that has long fired), and what this stream goes on with -- weights, sums, resample, the next dispersion and lane
     // order -- is shorter than the map update and off the chain.  With the scan-match kernel on this stream, the chain crossed
     // streams twice per frame (fork behind the best pose, join in front of the next scan-match), 12-17 us each.
-    static const bool aux_ok = !(ab_env("PFSLAM_SCORE_ON_AUX") && atoi(ab_env("PFSLAM_SCORE_ON_AUX")) == 0);
-    const bool on_aux = aux_ok && h->score_on_aux && use_cells && !cells_sync && fuse_minmax && !census && !sharded;
+    const bool on_aux = h->score_on_aux && use_cells && !cells_sync && fuse_minmax && !census && !sharded;
     h->scored_on_aux = on_aux;
     struct StreamSwap { // the rest of this function launches on h->stream: point it at the aux stream for that long
         pfslam_handle *h;
@@ -1831,15 +1809,14 @@ static int launch_score(pfslam_handle *h, bool fuse_minmax = false, pf::KdCensus
         if (use_cells) {
 #define PF_CELLS_ARGS grid64, dim3(64), 0, h->stream, h->x, h->y, h->th, h->n, h->scan, (const pf::BeamParts *)h->beam_angle, h->nb, bpc, kd_view(h), geo, \
                       (const unsigned *)h->cell_tab, (const uint4 *)h->cell_pool, (const int *)h->cell_state, order, direct
-            // a census replay BEHIND an accumulating pass must not add its (identical) sums a second time
             // no heading anywhere near the bound of the angle-addition sincos (the host's running bound, refreshed from every frame's
             // header): the instantiation without the direct form -- 60 instead of 79 VGPRs, 8 instead of 6 waves per SIMD
             const bool guard = !(h->theta_bound < 0.5f * PF_SUM_THETA_MAX) || h->own_global; // (a shard imports particles at every resample: always guarded)
-            if (h->trig && cen) hipLaunchKernelGGL((k_score_kd_cells<true, PF_TRIG_DEVLIB>), PF_CELLS_ARGS, acc_out ? h->fit_acc : out, acc_out ? 2 : p16 ? 3 : 0, cen);
-            else if (h->trig) hipLaunchKernelGGL((k_score_kd_cells<false, PF_TRIG_DEVLIB>), PF_CELLS_ARGS, acc_out ? h->fit_acc : out, acc_out ? 1 : p16 ? 3 : 0, (pf::KdCensus *)nullptr);
-            else if (cen) hipLaunchKernelGGL((k_score_kd_cells<true, true>), PF_CELLS_ARGS, acc_out ? h->fit_acc : out, acc_out ? 2 : p16 ? 3 : 0, cen);
-            else if (guard) hipLaunchKernelGGL((k_score_kd_cells<false, true>), PF_CELLS_ARGS, acc_out ? h->fit_acc : out, acc_out ? 1 : p16 ? 3 : 0, (pf::KdCensus *)nullptr);
-            else hipLaunchKernelGGL((k_score_kd_cells<false, false>), PF_CELLS_ARGS, acc_out ? h->fit_acc : out, acc_out ? 1 : p16 ? 3 : 0, (pf::KdCensus *)nullptr);
+            if (h->trig && cen) hipLaunchKernelGGL((k_score_kd_cells<true, PF_TRIG_DEVLIB>), PF_CELLS_ARGS, out, p16 ? 3 : 0, cen);
+            else if (h->trig) hipLaunchKernelGGL((k_score_kd_cells<false, PF_TRIG_DEVLIB>), PF_CELLS_ARGS, out, p16 ? 3 : 0, (pf::KdCensus *)nullptr);
+            else if (cen) hipLaunchKernelGGL((k_score_kd_cells<true, true>), PF_CELLS_ARGS, out, p16 ? 3 : 0, cen);
+            else if (guard) hipLaunchKernelGGL((k_score_kd_cells<false, true>), PF_CELLS_ARGS, out, p16 ? 3 : 0, (pf::KdCensus *)nullptr);
+            else hipLaunchKernelGGL((k_score_kd_cells<false, false>), PF_CELLS_ARGS, out, p16 ? 3 : 0, (pf::KdCensus *)nullptr);
 #undef PF_CELLS_ARGS
         } else if (use_plan) {
             if (cen)
@@ -1901,9 +1878,8 @@ static int launch_score(pfslam_handle *h, bool fuse_minmax = false, pf::KdCensus
         HIPCHK(hipGetLastError());
     } else if (used > 1 && fuse_minmax) {
 #define PF_REDUCE4_WGS 128 /* workgroups of k_reduce_partials_minmax (grid-stride over the slots; see the kernel) */
-        static const int reduce4_wgs = ab_env("PFSLAM_REDUCE4_WGS") ? std::max(1, atoi(ab_env("PFSLAM_REDUCE4_WGS"))) : PF_REDUCE4_WGS; // (A/B: 1000000 = one workgroup per 256 slots)
-        hipLaunchKernelGGL(k_reduce_partials_minmax, dim3(std::min((h->n + 255) / 256, reduce4_wgs)), dim3(256), 0, h->stream, acc_out ? h->fit_acc : h->partial, h->n,
-                           acc_out ? 1 : used, order, h->fit, h->goff, (long long *)h->stats, h->x, h->y, h->th, acc_out ? 1 : 0, p16 ? 1 : 0);
+        hipLaunchKernelGGL(k_reduce_partials_minmax, dim3(std::min((h->n + 255) / 256, PF_REDUCE4_WGS)), dim3(256), 0, h->stream, h->partial, h->n,
+                           used, order, h->fit, h->goff, (long long *)h->stats, h->x, h->y, h->th, p16 ? 1 : 0);
         HIPCHK(hipGetLastError());
     } else {
         if (used > 1) {

@@ -92,12 +92,10 @@ __global__ void k_stats_reset(long long *stats)
 
 // k_reduce_partials + k_minmax<float> in one launch (the frame loop's chain is bounded by its number of dependent
 // launches): same chunk-order sum per slot, then the packed keys of the block go into stats with two atomics.
-// wipe: the partials are the scan-match kernel's accumulators (one per lane, atomically added to): their reader zeroes them.
-__global__ __launch_bounds__(256) void k_reduce_partials_minmax(float *__restrict__ partial, int n, int chunks,
+__global__ __launch_bounds__(256) void k_reduce_partials_minmax(const float *__restrict__ partial, int n, int chunks,
                                                                 const int *__restrict__ order, float *__restrict__ fit, int goff,
                                                                 long long *__restrict__ stats, const float *__restrict__ x,
-                                                                const float *__restrict__ y, const float *__restrict__ th,
-                                                                int wipe, int p16)
+                                                                const float *__restrict__ y, const float *__restrict__ th, int p16)
 {
     // At most PF_REDUCE4_WGS workgroups take the slots in a grid-stride loop: one workgroup per 256 slots ended with three atomics (and, sharded,
     // a fence) on ONE cache line each -- 391 workgroups at 100 k particles, applied one after the other, and the launch behind this one
@@ -134,7 +132,6 @@ __global__ __launch_bounds__(256) void k_reduce_partials_minmax(float *__restric
             for (int k = 0; k < 16; k++) a += v[k];
         }
         for (; c < chunks; c++) a += partial[(size_t)c * n + slot];
-        if (wipe) partial[slot] = 0.0f; // chunks == 1
         const int i = order ? order[slot] : slot;
         fit[i] = a;
         const long long k1 = ((long long)f32_to_ordered(a) << 32) | (long long)(0xFFFFFFFFu - (uint32_t)(goff + i));
@@ -1856,10 +1853,9 @@ static int fork_icp(pfslam_handle *h)
     // on a stream of its own: it needs the tree as the previous frame's insert left it (ev_tree), not that frame's k_cells_update,
     // which follows on the aux stream -- queued behind that, the solve started when the scan-match kernel did and its one
     // 1024-thread workgroup took 340 us instead of 33 among the 131 k single-wave workgroups
-    static const bool own = !(ab_env("PFSLAM_ICP_STREAM") && atoi(ab_env("PFSLAM_ICP_STREAM")) == 0);
     // (only when the cell rows are in use: without a k_cells_update behind the insert the aux stream is free in time, and the extra
     // cross-stream hop costs the launch-bound frame of a small particle count 15 us: 0.187 vs 0.170 ms at 1000 particles)
-    const bool own_now = own && h->cells_valid;
+    const bool own_now = h->cells_valid;
     hipStream_t st = own_now ? h->istream : h->aux;
     HIPCHK(hipStreamWaitEvent(st, h->ev_fork, 0));
     if (own_now && h->tree_event) HIPCHK(hipStreamWaitEvent(st, h->ev_tree, 0));
@@ -2632,8 +2628,6 @@ static bool balance_due(const pfslam_handle *h, int frame)
 static int balance_if_due(pfslam_handle *h, int frame)
 {
     if (!(balance_due(h, frame) && h->kd_size > 0)) return 0;
-    static const bool dbg = ab_env("PFSLAM_DEBUG_BALANCE") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
     // KDTree::Balance re-creates the tree from the current node VALUES in array order (kdtree.cpp:31-40): positions of the nodes the
     // host has seen are in its mirror, so only the weights (every frame changes them) and the records of the nodes the device has
     // appended since come back -- not the links, which the re-build discards
@@ -2664,17 +2658,9 @@ static int balance_if_due(pfslam_handle *h, int frame)
             }
         });
     }
-    const auto t1 = std::chrono::steady_clock::now();
     std::vector<pfslam_node> tmp(K);
     if (pfslam_kd_create(pts.data(), n, tmp.data())) return fail("kd_balance failed");
-    const auto t2 = std::chrono::steady_clock::now();
-    const int rc = upload_tree(h, tmp.data(), n, &tmp);
-    if (dbg) {
-        const auto t3 = std::chrono::steady_clock::now();
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "balance frame %d: %d nodes, read-back %.2f ms, KDTree::Balance %.2f ms, upload %.2f ms\n", frame, n, ms(t0, t1), ms(t1, t2), ms(t2, t3));
-    }
-    return rc;
+    return upload_tree(h, tmp.data(), n, &tmp);
 }
 // ---- multi-GPU: ONE KDTree::Balance per node ---------------------------------------------------------------------------------
 // Every rank holds the same map, so by default every rank of a sharded job would re-build it at frame % period == 5 -- eight

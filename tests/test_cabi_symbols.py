@@ -69,20 +69,30 @@ def test_whole_node_thread_budget():
 
 
 def test_environment_switches_are_the_documented_set():
-    """Housekeeping of round 6: the product build reads only the test / diagnostic switches tools/README.md lists; the A/B knobs of past
-    experiments go through ab_env(), which is getenv only under -DPF_EXPERIMENTS (not among the build's flags)."""
+    """The library reads only the test / diagnostic switches tools/README.md lists, and INTEGRATION.md names no other; the A/B knobs of
+    past experiments (runtime ab_env() switches and compile-time selectors) are folded to their defaults and gone from the source."""
     import glob
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     allowed = {"PFSLAM_SERIAL", "PFSLAM_GATES", "PFSLAM_FAULT", "PFSLAM_STABLE_ORDER", "PFSLAM_MARK_EARLY", "PFSLAM_PUBLISH_LAG", "PFSLAM_VARIANT",
                "PFSLAM_PLAN_MIN_N", "PFSLAM_CELL_LIST_CAP", "PFSLAM_CELL_POOL_CAP", "PFSLAM_SORT_THREADS", "PFSLAM_PLAIN_SORT", "PFSLAM_VERBOSE"}
+    gone = ("ab_env", "PF_EXPERIMENTS", "PF_ROW_GROW", "PF_CU_HOIST", "PF_CU_LAST", "PF_CU_NOCORNER", "PF_SETPRIO")
     read = set()
     for f in glob.glob(os.path.join(root, "gpu-icp-slam_amd", "csrc", "*")):
+        if not os.path.isfile(f):
+            continue
+        src = open(f, errors="replace").read()
+        found = [w for w in gone if w in src]
+        assert not found, "%s still holds %s" % (os.path.basename(f), found)
         if f.endswith((".hip", ".inc", ".h", ".cpp")):
-            src = open(f).read()
             read |= set(re.findall(r'[^_a-z]getenv\("(PFSLAM_[A-Z0-9_]+)"\)', src))
     assert read <= allowed, "undocumented environment switch in the product build: %s" % sorted(read - allowed)
     readme = open(os.path.join(root, "tools", "README.md")).read()
     assert all(name in readme for name in read)
     build = open(os.path.join(root, "gpu-icp-slam_amd", "build.py")).read()
     assert "PF_EXPERIMENTS" not in build.split("FLAGS =")[1].split("\n")[0]
+    # the library's switches as INTEGRATION.md presents them: the paragraph that starts "Environment switches of `libpfslam_hip.so`"
+    integ = open(os.path.join(root, "INTEGRATION.md")).read()
+    para = integ[integ.index("Environment switches of `libpfslam_hip.so`"):].split("\n\n")[0]
+    documented = set(re.findall(r"PFSLAM_[A-Z0-9_]+", para))
+    assert documented and documented <= allowed, "INTEGRATION.md presents switches the library does not read: %s" % sorted(documented - allowed)
