@@ -1163,8 +1163,20 @@ static int probe_slot_ptr(pfslam_handle *h, int id, unsigned long long **out)
 //                      [all-gather of the 16-byte keys 14 -> 15 on C: the one collective on the frame's critical chain]
 //   part 2 (chain)     C: walls (say REDUCED; wait for ICP and POSEG), traversals, insert, cell rows.   P: [gate REDUCED] weights.
 //                      [all-gather of the weights 5 -> 10 on P]
-//   part 3 (finish)    P: sums on the (gathered) weights, header part A, gated resample out of the (gathered) pose blocks.   F: free cells,
-//                      weight passes, header part B.   Booking.
+//   part 3 (finish)    P: sums on the (gathered) weights, header part A, gated resample out of the (gathered) pose blocks.   F: [wait POSEG]
+//                      free cells, weight passes, header part B.   Booking.
+// What orders the readers of the gathered buffers (world > 1; tests/test_gpu_sharded_async.py holds each collective back for many frames):
+//   17 pose blocks (collective 0, P)   P: k_theta_gmax, k_weights_apply_sharded, k_sample_gather by stream order.  C: k_wall_runs / k_walls<0>
+//                                      wait for POSEG (k_theta_gmax's word, or ev_poseg).  F: k_get_walls and k_scatter_cells wait for POSEG
+//                                      too -- REDUCED does not cover them: k_wall_runs says REDUCED before its own POSEG wait.
+//   15 keys (collective 1, C; P in a one-stream frame)   C: k_wall_runs / k_walls by stream order.  P (k_weights_apply_sharded) and F
+//                                      (k_get_walls, k_scatter_cells) wait for REDUCED, which C raises behind the collective.
+//   10 weights (collective 2, P)       read on P only (k_weight_scan_tiles, k_scan_apply2, k_sample_gather).
+//   next frame's collectives           0 and 2 ride P behind its FTAIL(f) wait (gate or ev_ftail), and FTAIL(f) lies behind every reader of
+//                                      frame f on F and, through TREE(f), on C; 1 rides C behind ORDER(f + 1), which P raises behind that
+//                                      wait.  A one-stream frame joins all four streams first (join_all).
+//   staged chain                       every collective and reader on the handle's stream; its aux-stream map update starts behind an
+//                                      event recorded there after k_weights_apply_sharded and reads the pose that kernel wrote, not 15 / 17.
 // The caller has staged nothing yet: scan upload, re-balance and the first scan are handled here / by the caller as in frame_front.
 struct FvCtx {
     hipStream_t P, C, F, K;
@@ -1572,6 +1584,10 @@ static int frame_v2_finish(pfslam_handle *h)
     // ---- F: the free cells (rays, lists, -1 pass on the tree before the insert), then the walls' +4 and header part B ----
     {
         FV_EDGE_WAIT(F, PF_FL_REDUCED, h->ev_reduced, 0);
+        // (sharded: k_get_walls and k_scatter_cells read the best particle's pose out of the gathered pose blocks.  REDUCED does not cover
+        // them -- k_wall_runs says REDUCED before it waits for POSEG, and ev_reduced is recorded in front of C's wait for ev_poseg -- so the
+        // pose blocks' all-gather may still be running when the keys' has long finished)
+        if (c.multi) FV_EDGE_WAIT(F, PF_FL_POSEG, h->ev_poseg, 0);
         const int cx = (int)roundf(0.5f * h->dimx + h->cfg.map_res_x / 2), cy = (int)roundf(0.5f * h->dimy + h->cfg.map_res_y / 2);
         const int M = h->dimx * h->dimy, nblk = (M + 4095) / 4096;
         if (!h->masks_cleared) HIPCHK(hipMemsetAsync(h->free_mask, 0, (size_t)2 * M, F));

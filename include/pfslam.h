@@ -214,6 +214,9 @@ int pfslam_kd_size(pfslam_handle *h);
  *   [all-gather buffer 5 -> buffer 10, stream 0]    weights, shard_stride floats per rank
  *   pfslam_shard_finish     sums + Neff on the gathered weights, frame header, gated resample (sources from buffer 17); the free
  *                           cells' chain of the replicated map update; booking of the frame `lag` steps back
+ * The library orders every reader of buffers 10 / 15 / 17 behind the collective that fills it (the stream it rides, or an edge from it:
+ * the chain and free-cell streams wait for the pose blocks through k_theta_gmax on stream 0), and every collective of the next frame
+ * behind this frame's last readers of its buffer; the edge list is in csrc/pfslam_frame.hip.inc.
  * Results are bit-identical for any number of ranks.  Buffers 14 and 16 alternate between two allocations from frame to frame: query
  * 16 after pfslam_shard_disperse, 14 after pfslam_shard_score of the same frame.
  * A handle that holds ALL particles (global_n == n_particles) may be driven through the same calls (world 1): buffers 10 / 17
