@@ -156,6 +156,10 @@ static_assert(PF_CELL_SUB == 2, "sub_index / sub_edges halve the lattice cell");
 // moves by at most (|cy| + |r| d) d in x and (|cx| + |r| d) d in y; eps covers the lanes' float rounding and the 1-ulp sincos
 // many times over, and the rounding of rot = angle + theta itself, which grows with |theta| (headings are never normalised):
 // the centre and every lane each round their own sum to 0.5 ulp(|rot|) <= 2^-24 (|theta| + 2.36).
+// The box is the SPECIFICATION's in both arithmetic modes (pfslam_set_trig): the marking pass does not look at the mode, eps covers the
+// last-place differences of the device library's cosf / sinf, and a lane whose end point lands in a cell nobody marked finds no row there
+// and takes the generic traversal (tests/test_gpu_devlib_frames.py, test_marking_pass_does_not_look_at_the_mode: same bookkeeping in
+// either mode; the frames and scores of that file hold the device-library lanes to the reference's kernel on those rows).
 // false: no box (non-finite or absurd geometry, NaN poses, or a beam no heading can accept: |r| >= PF_RANGE_NEVER).
 // T / beams: the centre heading's parts (k_group_box) and the beam table -- the same end point for 15 double operations instead of
 // two argument reductions and polynomials (a marking thread computes one per (group, beam)); nullptr: from scratch.

@@ -2383,6 +2383,9 @@ extern "C" int pfslam_device_ptr(pfslam_handle *h, int which, void **ptr, size_t
     case 8: *ptr = h->start; *bytes = 16; break;
     case 9: *ptr = h->pose; *bytes = 16; break;
     case 10: *ptr = h->gw; *bytes = (size_t)h->world * h->stride * 4; break;
+    // what the last ICP left behind (pfslam_icp's k_icp_correspond, a frame's k_icp_fused): kernGetWallsKD's targets and their matched nodes
+    case 11: *ptr = h->icp_tar; *bytes = (size_t)h->nb * 16; break;
+    case 12: *ptr = h->icp_cor; *bytes = (size_t)h->nb * 16; break;
     // this rank's record of the frame being enqueued = its packed {max key, negated-min key}, straight from the reduce: query it after
     // pfslam_shard_score of the same frame (round-5 frames keep two of them, by ticket parity); 15 = every rank's record
     case 14: *ptr = (h->shard_v2 && h->fstats) ? (void *)(h->fstats + 4 * (h->cur_seq & 1)) : (void *)h->stats; *bytes = 16; break;

@@ -246,6 +246,10 @@ int pfslam_measurement_apply(pfslam_handle *h, int *best_global, float *fmin, fl
  * which: 0 stats (8 x i64), 1 fit (n x f32), 2 x, 3 y, 4 theta (n x f32 each; inside buffer 16), 5 w (shard_stride x f32, the
  *        first n valid), 6 weight tile sums, 7 scan (n_beams x f32), 8 best-particle pose (4 x f32), 9 robot pose (4 x f32),
  *        10 global w (world * shard_stride x f32, rank-major, the first global_n valid; aliases 5 when unsharded),
+ *        11 ICP targets, 12 ICP correspondences (n_beams x float4 each): what the last ICP left behind -- kernGetWallsKD's target cloud at
+ *        the previous pose (rejected beams: zero, H2) and findCorrespondenceKD's matched node (x, y, z, w) of every target, as pfslam_icp
+ *        writes them; a frame of pfslam_step leaves the same arrays with w = 0 in the correspondences (test support:
+ *        tests/test_gpu_devlib_frames.py compares them with the reference's kernels),
  *        14 this rank's 16-byte measurement record (its packed max / negated-min keys), 15 the gathered records (world x 16 B),
  *        16 local pose block [x | y | theta] (3 * shard_stride x f32; moves when a resample swaps the double buffer),
  *        17 global pose blocks (world x 3 * shard_stride x f32, rank-major; aliases 16 when unsharded) */
@@ -305,7 +309,9 @@ int pfslam_set_variant(pfslam_handle *h, int variant);
 /* Transcendentals.  0 (default) = the specification of csrc/pf_math.h: fixed sequences of IEEE double operations rounded once, which the
  * CPU oracle follows bit for bit.  1 = the device library's cosf / sinf in CleanLidarScan (kernel.cu:182-187) and erfcinvf in the
  * dispersion (kernel.cu:375-397) -- what the reference's own text compiles to on this platform: with it the product's kernels equal the
- * reference's kernels built for gfx950 with zero mismatches (tests/test_gpu_ref_kernels.py); results then differ from the oracle's in
+ * reference's kernels built for gfx950 with zero mismatches (tests/test_gpu_ref_kernels.py: the stage entry points;
+ * tests/test_gpu_devlib_frames.py: whole frames of pfslam_step / pfslam_step_grid / pfslam_shard_* against a frame composed of those
+ * stage calls, and the frame's own scan-match and ICP launches against the reference's kernels); results then differ from the oracle's in
  * the last place of an end point now and then. */
 int pfslam_set_trig(pfslam_handle *h, int devlib);
 /* ---- round-5 frame loop: test and measurement support (no reference counterpart) ----

@@ -1,6 +1,8 @@
 """Differential fuzz of the whole frame loop (KD and 2-D variants) against the oracle: random configurations and adversarial
 scans (NaN / Inf / zero / out-of-range beams, robot driven to the map edge, tiny capacity headroom).  Run on the GPU box:
-    python tests/fuzz_step.py [seconds] [seed]
+    python tests/fuzz_step.py [--devlib] [seconds] [seed]
+--devlib: device-library mode (pfslam_set_trig(1)) on the product, and the comparator is tests/stage_shadow.py -- a second handle stepped
+stage by stage, in the same mode -- instead of the CPU oracle, which cannot follow that mode; everything else is unchanged.
 Exits non-zero at the first divergence and prints the case."""
 import importlib, os, sys, time
 import numpy as np
@@ -9,6 +11,10 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import oracle_lib as O
 pkg = importlib.import_module("gpu-icp-slam_amd")
 os.environ.setdefault("ORC_THREADS", str(min(64, os.cpu_count() or 1)))
+DEVLIB = "--devlib" in sys.argv[1:]
+if DEVLIB:
+    sys.argv.remove("--devlib")
+    from stage_shadow import StageShadow
 
 # python tests/fuzz_step.py --replay FILE : the case a diverging run saved (gpurun_out/fuzz_case.npz), stepped again with a look at every frame
 REPLAY = None
@@ -53,9 +59,15 @@ while time.time() < t_end:
     desc = dict(n=n, nb=nb, res=res, scale=scale, strict=strict, bug=bug, period=period, grid=grid_mode, nframes=nframes, seed=seed, cap=cap)
     patch = O.Patch(scale, scale, res, res)
     try:
-        o = O.Slam(n, n_beams=nb, kd_capacity=cap, strict_host_mirror=strict, free_upload_bug=bug, balance_period=period, patch=patch)
+        if DEVLIB:
+            o = StageShadow(n, n_beams=nb, kd_capacity=cap, strict_host_mirror=strict, free_upload_bug=bug, balance_period=period,
+                            map_scale=(scale, scale), map_res=(res, res), trig=1, pkg=pkg)
+        else:
+            o = O.Slam(n, n_beams=nb, kd_capacity=cap, strict_host_mirror=strict, free_upload_bug=bug, balance_period=period, patch=patch)
         h = pkg.PfSlam(n, n_beams=nb, kd_capacity=cap, strict_host_mirror=strict, free_upload_bug=bug, balance_period=period,
                        map_scale=(scale, scale), map_res=(res, res))
+        if DEVLIB:
+            h.set_trig(1)
     except pkg.PfSlamError as e:
         print("create refused", desc, e); continue
     drift = rng.rand() < 0.2  # push the particle cloud towards the map edge
@@ -117,4 +129,4 @@ while time.time() < t_end:
             print("DIVERGED particles", fld, desc); sys.exit(1)
     h.close(); o.close()
     cases += 1
-print("fuzz ok: %d cases, %d frames (%d cases ended by a loud kd_capacity refusal)" % (cases, frames_total, refused))
+print("fuzz ok%s: %d cases, %d frames (%d cases ended by a loud kd_capacity refusal)" % (" (device library, against the stage shadow)" if DEVLIB else "", cases, frames_total, refused))

@@ -24,8 +24,10 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
-def run_frames(pkg, tree, scans, n, serial, variant=0, look_every=0, first_frame=6, env=None):
-    """Step `scans` through a fresh handle; returns (per-frame rows of trace + pose bits, particles, map bytes, bookkeeping, check)."""
+def run_frames(pkg, tree, scans, n, serial, variant=0, look_every=0, first_frame=6, env=None, prepare=None, inspect=None):
+    """Step `scans` through a fresh handle; returns (per-frame rows of trace + pose bits, particles, map bytes, bookkeeping, check).
+    prepare(h): called on the handle behind set_map / set_variant / set_serial (other test modules: set_trig, set_lag);
+    inspect(h): called behind the last frame, its result is appended to the tuple."""
     old = {}
     env = dict(env or {}, PFSLAM_STABLE_ORDER="1")  # (a canonical lane order: the counting sort's is arrival order inside a Hilbert cell)
     for k, v in env.items():
@@ -44,6 +46,8 @@ def run_frames(pkg, tree, scans, n, serial, variant=0, look_every=0, first_frame
         h.set_variant(variant)
     if serial:
         h.set_serial(1)
+    if prepare:
+        prepare(h)
     for f in range(1, 6):
         h.motion_update(f)
     rows = []
@@ -59,7 +63,10 @@ def run_frames(pkg, tree, scans, n, serial, variant=0, look_every=0, first_frame
     chk = h.check_cells()
     p = h.particles().copy()
     m = h.map().tobytes()
+    seen = inspect(h) if inspect else None
     h.close()
+    if inspect:
+        return rows, p, m, {k: st[k] for k in BOOK}, chk, seen
     return rows, p, m, {k: st[k] for k in BOOK}, chk
 
 
