@@ -25,7 +25,7 @@ SYMBOLS = [
     "pfslam_measurement_apply", "pfslam_device_ptr", "pfslam_time_score_kd", "pfslam_set_variant", "pfslam_set_lag",
     "pfslam_kd_create", "pfslam_kd_insert_list", "pfslam_kd_insert_node", "pfslam_kd_balance", "pfslam_set_timing", "pfslam_get_timers", "pfslam_resample_plan", "pfslam_resample_gather", "pfslam_maybe_balance", "pfslam_kd_size", "pfslam_topology_update", "pfslam_find_walls",
     "pfslam_check_loop_closure", "pfslam_get_topology", "pfslam_set_topology", "pfslam_get_closures", "pfslam_score_census", "pfslam_set_census", "pfslam_get_census_log", "pfslam_ubench_gather", "pfslam_plan_stats", "pfslam_cell_stats", "pfslam_kd_parallel_sort", "pfslam_kd_sort_threads", "pfslam_kd_whole_node",
-    "pfslam_set_serial", "pfslam_set_trig", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
+    "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
 
@@ -139,6 +139,7 @@ def load():
     L.pfslam_cell_stats.argtypes = [vp, vp]
     L.pfslam_set_serial.argtypes = [vp, i32]
     L.pfslam_set_trig.argtypes = [vp, i32]
+    L.pfslam_set_resampler.argtypes = [vp, i32]
     L.pfslam_debug_check_cells.argtypes = [vp, vp]
     L.pfslam_set_probe.argtypes = [vp, i32]
     L.pfslam_get_probe.argtypes = [vp, vp, i32, vp, vp]
@@ -510,6 +511,11 @@ class PfSlam:
     def set_trig(self, devlib):
         """1: the device library's cosf / sinf / erfcinvf instead of the pf_math.h specification (include/pfslam.h, pfslam_set_trig)."""
         _chk(self.L.pfslam_set_trig(self._h, 1 if devlib else 0), "pfslam_set_trig")
+
+    def set_resampler(self, mode):
+        """Where a resample's thread i takes its draw from: 0 the reference's seeding (512 distinct draws whatever N is, H5), 1 one
+        multinomial draw per particle, 2 systematic resampling (include/pfslam.h, pfslam_set_resampler).  Sharded: the same on every rank."""
+        _chk(self.L.pfslam_set_resampler(self._h, int(mode)), "pfslam_set_resampler")
 
     def frame_mode(self):
         out = (C.c_int * 4)()

@@ -1553,11 +1553,11 @@ static int frame_v2_finish(pfslam_handle *h)
             if (c.multi)
                 hipLaunchKernelGGL((k_sample_gather<true, true>), dim3((n + 255) / 256), dim3(256), 0, P, (const float *)h->cdf, (const float *)h->chunk_max,
                                    (const float *)h->tile_pmax, gn, n, h->goff, frame, (const float *)h->sums, h->src, (const float *)h->gpose, h->pblk2, h->stride, h->w,
-                                   h->wm, thr);
+                                   h->wm, thr, h->resampler);
             else
                 hipLaunchKernelGGL((k_sample_gather<true, false>), dim3((n + 255) / 256), dim3(256), 0, P, (const float *)h->cdf, (const float *)h->chunk_max,
                                    (const float *)h->tile_pmax, n, n, 0, frame, (const float *)h->sums, h->src, (const float *)h->pblk, h->pblk2, h->stride, h->w,
-                                   h->wm, thr);
+                                   h->wm, thr, h->resampler);
         } else {
             const int n = h->n;
             if (n <= PF_SUM_TILE) {
@@ -1565,7 +1565,7 @@ static int frame_v2_finish(pfslam_handle *h)
                                    h->x, h->y, h->th, (float *)nullptr, h->sums, (const float *)nullptr, h->pose);
                 hipLaunchKernelGGL(k_header_a, dim3(1), dim3(64), 0, P, (const float *)h->sums, (const long long *)c.stats, (const float *)c.sig, c.hdr, seq);
                 hipLaunchKernelGGL(k_resample_small, dim3(1), dim3(1024), 0, P, (const float *)h->w, n, h->cdf, h->chunk_max, h->tile_pmax, frame,
-                                   (const float *)h->sums, h->src, (const float *)h->pblk, h->pblk2, h->stride, h->w, h->wm, thr);
+                                   (const float *)h->sums, h->src, (const float *)h->pblk, h->pblk2, h->stride, h->w, h->wm, thr, h->resampler);
             } else {
                 const int nts = (n + PF_SUM_TILE - 1) / PF_SUM_TILE, nt = (n + PF_SCAN_TILE - 1) / PF_SCAN_TILE;
                 hipLaunchKernelGGL(k_weights_tiles, dim3(nts), dim3(256), 0, P, h->w, h->wm, (const float *)h->fit, n, mirror_count(h), (const long long *)c.stats,
@@ -1575,7 +1575,7 @@ static int frame_v2_finish(pfslam_handle *h)
                                    (const float *)c.sig, PB(PB_APPLY));
                 hipLaunchKernelGGL((k_sample_gather<true, false>), dim3((n + 255) / 256), dim3(256), 0, P, (const float *)h->cdf, (const float *)h->chunk_max,
                                    (const float *)h->tile_pmax, n, n, 0, frame, (const float *)h->sums, h->src, (const float *)h->pblk, h->pblk2, h->stride, h->w,
-                                   h->wm, thr);
+                                   h->wm, thr, h->resampler);
             }
         }
         HIPCHK(hipGetLastError());

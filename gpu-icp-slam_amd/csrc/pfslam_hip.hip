@@ -263,6 +263,7 @@ struct pfslam_handle {
     bool cells_snap = false;       // this frame's k_cells_update<true> may run beside the next frame's marking pass: records below the walk pass's snapshot only
     pf::BeamParts *beam_angle = nullptr; // LIDAR_ANGLE(j) and its cos / sin as doubles, nb entries
     // ---- round-5 frame loop (pfslam_frame.hip.inc): four in-order chains, a fixed set of events between them ----
+    int resampler = 0;            // pfslam_set_resampler: where a resample's thread i takes its rnd from (sample_rnd): 0 reference seeding, 1 per-particle, 2 systematic
     int trig = 0;                 // pfslam_set_trig: 1 = the device library's cosf / sinf / erfcinvf instead of the pf_math.h specification (see sincos_sum_spec)
     int serial = 0;               // PFSLAM_SERIAL=1: every frame's launches on ONE stream, in enqueue order (same results, same bookkeeping)
     bool pipe_live = false;       // the last frame was a round-5 frame: its events and ring slots are what the next one waits on
@@ -2239,6 +2240,16 @@ extern "C" int pfslam_set_trig(pfslam_handle *h, int devlib)
     HIPCHK(hipSetDevice(h->cfg.device));
     CHK(settle(h));
     h->trig = devlib;
+    return 0;
+}
+// The resample's draw (include/pfslam.h; sample_rnd in pfslam_stages.hip.inc): a kernel argument of launches that exist in every mode, so
+// nothing about streams, gates or edges depends on it.  Holds from the next stage call or enqueued frame.
+extern "C" int pfslam_set_resampler(pfslam_handle *h, int mode)
+{
+    if (!h || mode < 0 || mode > 2) return fail("pfslam_set_resampler: 0 (reference seeding), 1 (per-particle seeds) or 2 (systematic)");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    CHK(settle(h));
+    h->resampler = mode;
     return 0;
 }
 // 1: every frame's launches on one stream, in enqueue order (what PFSLAM_SERIAL=1 sets at creation); same results, same bookkeeping

@@ -1467,12 +1467,25 @@ __global__ __launch_bounds__(64) void k_weight_final_offsets(const float *__rest
 // rnd <= cdf[idx]; found through tile prefix-maxima, chunk maxima, then the chunk itself, which
 // is exact for any cdf (also a non-monotone one, H8).  The engine is seeded exactly as the
 // reference does, collisions included (H5).  gn = number of global particles (cdf length).
+// mode (pfslam_set_resampler, uniform over the launch) changes only where thread i takes its rnd from: 0 = the reference's seeding (the
+// particle index lands in the key's 9-bit field: 512 distinct draws whatever gn is); 1 = the same function with the particle index in
+// the argument that is hashed whole (one multinomial draw per particle); 2 = systematic: one draw u of the frame, rnd_i =
+// ((i + u) * maxv) / gn in double -- add, multiply, divide, in that order (nothing there can contract into an fma), rounded to float once.
+__device__ __forceinline__ float sample_rnd(float maxv, int gn, float neff, int frame, int global_i, int mode)
+{
+    if (mode == 2) {
+        uint32_t gen = pf::engine_seed((int)neff, frame, 0);
+        const float u = pf::uniform_real(gen, 0.0f, 1.0f);
+        return (float)((((double)global_i + (double)u) * (double)maxv) / (double)gn);
+    }
+    uint32_t gen = mode == 1 ? pf::engine_seed((int)neff, global_i, frame) : pf::engine_seed((int)neff, frame, global_i);
+    return pf::uniform_real(gen, 0.0f, maxv);
+}
 __device__ __forceinline__ int sample_index(const float *__restrict__ cdf, const float *__restrict__ chunk_max,
-                                            const float *__restrict__ tile_pmax, int gn, float neff, int frame, int global_i)
+                                            const float *__restrict__ tile_pmax, int gn, float neff, int frame, int global_i, int mode)
 {
     const float maxv = cdf[gn - 1];
-    uint32_t gen = pf::engine_seed((int)neff, frame, global_i);
-    const float rnd = pf::uniform_real(gen, 0.0f, maxv);
+    const float rnd = sample_rnd(maxv, gn, neff, frame, global_i, mode);
     const int nt = (gn + PF_SCAN_TILE - 1) / PF_SCAN_TILE;
     int lo = 0, hi = nt; // first tile with prefix-max >= rnd
     while (lo < hi) {
@@ -1497,12 +1510,12 @@ __device__ __forceinline__ int sample_index(const float *__restrict__ cdf, const
 __global__ __launch_bounds__(256) void k_sample(const float *__restrict__ cdf, const float *__restrict__ chunk_max,
                                                 const float *__restrict__ tile_pmax, int gn, int n, int goff, int frame,
                                                 const float *__restrict__ sums, int *__restrict__ src,
-                                                const float *__restrict__ gate, double thr)
+                                                const float *__restrict__ gate, double thr, int mode)
 {
     if (!resample_gate(gate, thr)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    src[i] = sample_index(cdf, chunk_max, tile_pmax, gn, sums[2], frame, goff + i);
+    src[i] = sample_index(cdf, chunk_max, tile_pmax, gn, sums[2], frame, goff + i, mode);
 }
 
 // Frame loops (unsharded): k_sample + k_gather in one launch that runs in EVERY frame and always moves the particles from one
@@ -1517,7 +1530,7 @@ __global__ __launch_bounds__(256) void k_sample_gather(const float *__restrict__
                                                        const float *__restrict__ tile_max, int gn, int n, int goff, int frame,
                                                        const float *__restrict__ sums, int *__restrict__ src,
                                                        const float *__restrict__ gpose, float *__restrict__ blk2, int stride,
-                                                       float *__restrict__ w, float *__restrict__ wm, double thr)
+                                                       float *__restrict__ w, float *__restrict__ wm, double thr, int mode)
 {
     __shared__ float s_pmax[LOCAL_PMAX ? PF_PMAX_LDS : 1];
     const bool doit = (double)sums[2] < thr;
@@ -1543,7 +1556,7 @@ __global__ __launch_bounds__(256) void k_sample_gather(const float *__restrict__
     if (i >= n) return;
     int s = goff + i;
     if (doit) {
-        s = sample_index(cdf, chunk_max, LOCAL_PMAX ? (const float *)s_pmax : tile_max, gn, sums[2], frame, goff + i);
+        s = sample_index(cdf, chunk_max, LOCAL_PMAX ? (const float *)s_pmax : tile_max, gn, sums[2], frame, goff + i, mode);
         src[i] = s;
         w[i] = 1.0f; // kernel.cu:441-442
         wm[i] = 1.0f;
@@ -1583,7 +1596,7 @@ __global__ __launch_bounds__(1024) void k_resample_small(const float *w_in, int 
                                                         float *__restrict__ chunk_max, float *__restrict__ tile_pmax, int frame,
                                                         const float *__restrict__ sums, int *__restrict__ src,
                                                         const float *__restrict__ blk, float *__restrict__ blk2, int stride,
-                                                        float *w, float *__restrict__ wm, double thr)
+                                                        float *w, float *__restrict__ wm, double thr, int mode)
 {
     const bool doit = (double)sums[2] < thr; // Neff < 0.7 N (kernel.cu:474)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1636,7 +1649,7 @@ __global__ __launch_bounds__(1024) void k_resample_small(const float *w_in, int 
     for (int i = threadIdx.x; i < n; i += 1024) { // k_sample_gather
         int sidx = i;
         if (doit) {
-            sidx = sample_index(cdf, chunk_max, tile_pmax, n, neff, frame, i);
+            sidx = sample_index(cdf, chunk_max, tile_pmax, n, neff, frame, i, mode);
             src[i] = sidx;
         }
         blk2[i] = blk[sidx];
@@ -2259,7 +2272,7 @@ static int launch_resample_plan(pfslam_handle *h, int frame, bool gated = false,
     hipLaunchKernelGGL(k_scan_pmax, dim3(1), dim3(64), 0, h->stream, h->tile_pmax, nt, gate, thr);
     if (with_sample)
         hipLaunchKernelGGL(k_sample, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->cdf, h->chunk_max, h->tile_pmax, gn, n, h->goff,
-                           frame, h->sums, h->src, gate, thr);
+                           frame, h->sums, h->src, gate, thr, h->resampler);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2277,7 +2290,7 @@ static int launch_resample(pfslam_handle *h, int frame, bool gated = false)
     if (gated && !h->own_global && h->n <= 4 * PF_SCAN_TILE) { // the reference's own sizes: one workgroup, one launch
         hipLaunchKernelGGL(k_resample_small, dim3(1), dim3(1024), 0, h->stream, (const float *)h->w, h->n, h->cdf, h->chunk_max,
                            h->tile_pmax, frame, (const float *)h->sums, h->src, (const float *)h->pblk, h->pblk2, h->stride, h->w,
-                           h->wm, PF_EFFECTIVE_PARTICLES * h->gn);
+                           h->wm, PF_EFFECTIVE_PARTICLES * h->gn, h->resampler);
         HIPCHK(hipGetLastError());
         swap_pose_blocks(h);
         return 0;
@@ -2296,7 +2309,7 @@ static int launch_resample(pfslam_handle *h, int frame, bool gated = false)
         h->scan_front_done = false;
         const dim3 g((n + 255) / 256);
 #define PF_SG_ARGS (const float *)h->cdf, (const float *)h->chunk_max, (const float *)h->tile_pmax, gn, n, h->goff, frame, (const float *)h->sums, \
-                   h->src, (const float *)h->gpose, h->pblk2, h->stride, h->w, h->wm, thr
+                   h->src, (const float *)h->gpose, h->pblk2, h->stride, h->w, h->wm, thr, h->resampler
         if (h->own_global) { // sources come from the all-gathered pose blocks of every rank
             if (local_pmax) hipLaunchKernelGGL((k_sample_gather<true, true>), g, dim3(256), 0, h->stream, PF_SG_ARGS);
             else hipLaunchKernelGGL((k_sample_gather<false, true>), g, dim3(256), 0, h->stream, PF_SG_ARGS);

@@ -164,6 +164,7 @@ static Scene *g_scene = nullptr;
 static int g_particles = 1000; // PARTICLE_COUNT, kernel.cu:30
 static glm::vec3 g_robotPos;
 static bool g_topology = false;
+static int g_resampler = 0; // pfslamSetResampler
 
 void checkPfslamErrorFn(int rc, const char *msg, const char *file, int line)
 {
@@ -197,6 +198,7 @@ void particleFilterInit(Scene *scene)
     PFCHK(pfslam_create(&cfg, &g_handle), "particleFilterInit");
     if (const char *e = getenv("PFSLAM_TOPOLOGY")) g_topology = atoi(e) != 0;
     PFCHK(pfslam_set_topology(g_handle, g_topology ? 1 : 0), "particleFilterInit (topology)");
+    PFCHK(pfslam_set_resampler(g_handle, g_resampler), "particleFilterInit (resampler)");
     g_robotPos = glm::vec3(0.0f);
     particleFilterInitPC();
 }
@@ -235,6 +237,11 @@ void pfslamUseTopology(bool on)
 {
     g_topology = on;
     if (g_handle) PFCHK(pfslam_set_topology(g_handle, on ? 1 : 0), "pfslamUseTopology");
+}
+void pfslamSetResampler(int mode)
+{
+    g_resampler = mode;
+    if (g_handle) PFCHK(pfslam_set_resampler(g_handle, mode), "pfslamSetResampler");
 }
 std::vector<std::pair<int, int>> pfslamLoopClosures()
 {

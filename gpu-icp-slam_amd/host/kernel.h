@@ -53,6 +53,10 @@ void pfslamUseGridMap(bool on);
 // (candidate node, visible node) pairs the last frame proposed.
 void pfslamUseTopology(bool on);
 std::vector<std::pair<int, int>> pfslamLoopClosures();
+// PFResample's draw (no reference counterpart; include/pfslam.h, pfslam_set_resampler): 0 = the reference's seeding, 512 distinct draws
+// whatever the particle count (default), 1 = one multinomial draw per particle, 2 = systematic resampling.  Read by the next
+// particleFilterInit (a live filter takes it from its next frame); a mode outside 0..2 prints and exits like every other error.
+void pfslamSetResampler(int mode);
 // Map export for an end-to-end comparison: the point-cloud map as the reference's viewer filters it
 // (nodes with w > -100, main.cpp:269-284) -> PREFIX.kd.bin (float x, y, z, w per point, in node order) + PREFIX.kd.csv, and
 // the 2-D occupancy grid -> PREFIX.grid.i8 (dim.x * dim.y signed bytes, cell (x, y) at x * dim.x + y) + PREFIX.grid.pgm

@@ -1,8 +1,9 @@
 // replay_main.cpp -- headless counterpart of the reference's main loop (main.cpp:47-96, 175-229):
-//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [export=PREFIX]
+//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [export=PREFIX]
 //     grid           the 2-D occupancy-grid stages instead of the point-cloud ones
 //     loop           UpdateTopology + CheckLoopClosure at the end of every frame (kernel.cu:1750-1751, commented out in
 //                    the reference's shipped step); loop-closure proposals are printed per frame
+//     resampler=N    PFResample's draw (pfslamSetResampler): 0 the reference's seeding (default), 1 per-particle seeds, 2 systematic
 //     export=PREFIX  after the last frame: the map as the reference's viewer filters it (KD nodes with w > -100,
 //                    main.cpp:269-284) and the occupancy grid -> PREFIX.kd.bin / .kd.csv / .grid.i8 / .grid.pgm
 // iteration 0: Free + Init; then particleFilter(pbo=NULL, ++iteration, lidar) until the scans run out.
@@ -17,7 +18,7 @@
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [export=PREFIX]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [export=PREFIX]\n", argv[0]);
         return 1;
     }
     Scene *scene = new Scene(argv[1]);
@@ -28,6 +29,7 @@ int main(int argc, char **argv)
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "grid") == 0) pfslamUseGridMap(true);
         else if (strcmp(argv[i], "loop") == 0) loop = true;
+        else if (strncmp(argv[i], "resampler=", 10) == 0) pfslamSetResampler(atoi(argv[i] + 10));
         else if (strncmp(argv[i], "export=", 7) == 0) export_prefix = argv[i] + 7;
         else if (atoi(argv[i]) > 0) last = std::min(last, (size_t)atoi(argv[i]));
     }

@@ -121,6 +121,7 @@ class ShardedSlam:
     # -- pass-throughs
     def set_map(self, tree): self.eng.set_map(tree)
     def set_variant(self, v): self.eng.set_variant(v)
+    def set_resampler(self, mode): self.eng.set_resampler(mode)   # (every rank the same mode: pfslam_set_resampler)
     def set_timing(self, e): self.eng.set_timing(e)
     def timers(self): return self.eng.timers()
     def motion_update(self, frame): self.eng.motion_update(frame)

@@ -314,6 +314,29 @@ int pfslam_set_variant(pfslam_handle *h, int variant);
  * stage calls, and the frame's own scan-match and ICP launches against the reference's kernels); results then differ from the oracle's in
  * the last place of an end point now and then. */
 int pfslam_set_trig(pfslam_handle *h, int devlib);
+/* Resampler: where thread i of a resample takes its rnd from.  Everything else of PFResample is the same in every mode, bit for bit: Neff
+ * from the canonical sums, the gate Neff < 0.7 N decided on the device, the inclusive scan, "first idx with rnd <= cdf[idx]" (exact for a
+ * non-monotone cdf too, H8), the gather from a snapshot (H3), w = 1 afterwards, the H11 mirror.  With i the GLOBAL particle index, gn the
+ * global particle count and maxv = cdf[gn - 1]:
+ *   0 (default) = the reference's scheme (kernel.cu:429-444), collisions included (H5):
+ *       rnd_i = uniform_real(engine_seed((int)Neff, frame, i), 0, maxv)
+ *     engine_seed(iter, index, depth) hashes the key (1 << 31) | (depth << 22) | iter, so i contributes its low 9 bits only: every resample
+ *     draws 512 distinct numbers whatever gn is, and a resampled cloud holds at most 512 distinct poses.
+ *   1 = one multinomial draw per particle, from the same seeding function with the particle index in the argument that is hashed whole:
+ *       rnd_i = uniform_real(engine_seed((int)Neff, i, frame), 0, maxv)
+ *     utilhash is a bijection on 32 bits, so seeds collide only through the final % (2^31 - 1) (999 870 distinct seeds among 1 000 000
+ *     particles).  The frame number now lands in the 9-bit field: two frames 512 apart that also share (int)Neff draw alike.
+ *   2 = systematic (low-variance) resampling, one draw per frame:
+ *       u     = uniform_real(engine_seed((int)Neff, frame, 0), 0.0f, 1.0f)
+ *       rnd_i = (float)((((double)i + (double)u) * (double)maxv) / (double)gn)
+ *     in exactly this order, in double, rounded to float once.  For positive weights the sources are non-decreasing in i and every particle
+ *     is copied floor or ceil of its expectation gn * w / sum(w) times.
+ * Above 512 particles a caller who does not need parity with the reference should choose 2.
+ * Like every entry point but the step functions the call first books the frames in flight; the mode holds from the next stage call or
+ * enqueued frame.  A mode outside 0..2 returns non-zero (pfslam_last_error) and leaves the handle's mode as it was.  On a sharded job EVERY
+ * rank must set the same mode (the caller's duty: nothing checks it); the draw depends on global quantities only, so results then stay
+ * bit-identical for any number of ranks. */
+int pfslam_set_resampler(pfslam_handle *h, int mode);
 /* ---- round-5 frame loop: test and measurement support (no reference counterpart) ----
  * pfslam_set_serial(h, 1): every launch of every frame on ONE stream, in the order the four chains of a frame are enqueued (what the
  * environment variable PFSLAM_SERIAL=1 sets at creation).  Results and the cell rows' bookkeeping are the same as with the chains on their
