@@ -25,7 +25,7 @@ SYMBOLS = [
     "pfslam_measurement_apply", "pfslam_device_ptr", "pfslam_time_score_kd", "pfslam_set_variant", "pfslam_set_lag",
     "pfslam_kd_create", "pfslam_kd_insert_list", "pfslam_kd_insert_node", "pfslam_kd_balance", "pfslam_set_timing", "pfslam_get_timers", "pfslam_resample_plan", "pfslam_resample_gather", "pfslam_maybe_balance", "pfslam_kd_size", "pfslam_topology_update", "pfslam_find_walls",
     "pfslam_check_loop_closure", "pfslam_get_topology", "pfslam_set_topology", "pfslam_get_closures", "pfslam_score_census", "pfslam_set_census", "pfslam_get_census_log", "pfslam_ubench_gather", "pfslam_plan_stats", "pfslam_cell_stats", "pfslam_kd_parallel_sort", "pfslam_kd_sort_threads", "pfslam_kd_whole_node",
-    "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
+    "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_estimate", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
 
@@ -140,6 +140,7 @@ def load():
     L.pfslam_set_serial.argtypes = [vp, i32]
     L.pfslam_set_trig.argtypes = [vp, i32]
     L.pfslam_set_resampler.argtypes = [vp, i32]
+    L.pfslam_estimate.argtypes = [vp, vp]
     L.pfslam_debug_check_cells.argtypes = [vp, vp]
     L.pfslam_set_probe.argtypes = [vp, i32]
     L.pfslam_get_probe.argtypes = [vp, vp, i32, vp, vp]
@@ -177,6 +178,14 @@ def _chk(rc, what=""):
 
 def device_count():
     return load().pfslam_device_count()
+
+
+def estimate_dict(out16):
+    """pfslam_estimate's 16 floats -> mean (3), cov (3 x 3, symmetric), neff, sum_w, sum_w2, n."""
+    o = np.asarray(out16, np.float32)
+    xx, xy, xt, yy, yt, tt = o[3:9]
+    return {"mean": o[0:3].copy(), "cov": np.array([[xx, xy, xt], [xy, yy, yt], [xt, yt, tt]], np.float32),
+            "neff": float(o[9]), "sum_w": float(o[10]), "sum_w2": float(o[11]), "n": int(o[12])}
 
 
 # ---- host-side map structure (no GPU needed) -------------------------------------------------
@@ -516,6 +525,17 @@ class PfSlam:
         """Where a resample's thread i takes its draw from: 0 the reference's seeding (512 distinct draws whatever N is, H5), 1 one
         multinomial draw per particle, 2 systematic resampling (include/pfslam.h, pfslam_set_resampler).  Sharded: the same on every rank."""
         _chk(self.L.pfslam_set_resampler(self._h, int(mode)), "pfslam_set_resampler")
+
+    def estimate_raw(self):
+        """The 16 floats of pfslam_estimate (include/pfslam.h) as a float32 array."""
+        out = np.zeros(16, np.float32)
+        _chk(self.L.pfslam_estimate(self._h, _p(out)), "pfslam_estimate")
+        return out
+
+    def estimate(self):
+        """Weighted mean pose, 3x3 covariance and Neff of the cloud, reduced on the device (include/pfslam.h, pfslam_estimate): the heading
+        mean is linear.  Sharded handles: buffers 10 and 17 must hold the gathered weights and pose blocks (ShardedSlam.estimate does that)."""
+        return estimate_dict(self.estimate_raw())
 
     def frame_mode(self):
         out = (C.c_int * 4)()

@@ -149,6 +149,7 @@ struct pfslam_handle {
     float *tile_r = nullptr, *tile_r2 = nullptr, *sums = nullptr; // sums: [r, r2, neff]
     float *cdf = nullptr, *chunk_max = nullptr, *tile_tot = nullptr, *tile_off = nullptr, *tile_pmax = nullptr;
     int *src = nullptr;
+    float *est_part = nullptr; // pfslam_estimate: 11 tile sums per 4096-particle tile of the GLOBAL cloud, then the 16 output floats
     // grid path
     int8_t *grid = nullptr;
     int32_t *fit_i = nullptr;
@@ -944,6 +945,7 @@ static int create_impl(pfslam_handle *h)
     CHK(dalloc(&h->cdf, G)); CHK(dalloc(&h->chunk_max, (G + PF_SCAN_CHUNK - 1) / PF_SCAN_CHUNK));
     CHK(dalloc(&h->tile_tot, nt_scan)); CHK(dalloc(&h->tile_off, nt_scan)); CHK(dalloc(&h->tile_pmax, nt_scan));
     CHK(dalloc(&h->src, n));
+    if (nt_sum <= PF_SUM_TILE) CHK(dalloc(&h->est_part, 11 * nt_sum + 16)); // (more tiles than that: pfslam_estimate refuses)
     CHK(dalloc(&h->grid, M));
     CHK(dalloc(&h->d_count, 4));
     CHK(dalloc(&h->wall_leaf, (size_t)h->max_wall));
@@ -1027,7 +1029,7 @@ extern "C" int pfslam_destroy(pfslam_handle *h)
                     h->fit, h->fit_i, h->partial, h->mkey, h->order2, h->cells, h->stats, h->pose, h->start, h->icp_tar, h->icp_cor, h->icp_dbg,
                     h->free_mask, h->blk_cnt, h->wall_cell, h->free_cell, h->wall_pts, h->free_pts,
                     h->wall_c, h->free_c, h->counts, h->tile_r, h->tile_r2, h->sums, h->cdf,
-                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
+                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (h->own_global) {

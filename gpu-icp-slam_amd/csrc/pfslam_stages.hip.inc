@@ -2364,6 +2364,147 @@ extern "C" int pfslam_resample(pfslam_handle *h, int frame, int *resampled, floa
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// pfslam_estimate: weighted mean pose and 3x3 covariance of the cloud (no reference counterpart; specification in include/pfslam.h).
+// Every sum is the canonical one over GLOBAL particle indices: tile t holds the particles [t * 4096, min((t + 1) * 4096, gn)) whatever
+// the sharding, its eleven sums are one wave each (wave_sum_canonical out of LDS), and the tile sums are summed the same way.
+//   part[q * nt + t], q = 0 w, 1 w*w, 2 w*x, 3 w*y, 4 w*theta (pass A), 5 .. 10 xx, xy, xtheta, yy, ytheta, thetatheta (pass B)
+// Particle g of the rank-major buffers: weight gw[g]; pose in block g / stride at g % stride ([x | y | theta], stride floats each).
+// ------------------------------------------------------------------------------------------
+#define PF_EST_WAVES 6
+__device__ __forceinline__ void est_stage(float (*s)[PF_SUM_TILE], const float *gw, const float *gpose, int stride, int g0, int cnt)
+{
+    for (int i = threadIdx.x; i < cnt; i += PF_EST_WAVES * 64) {
+        const int g = g0 + i;
+        const int r = g / stride, j = g - r * stride;
+        const float *blk = gpose + (size_t)r * 3 * stride;
+        s[0][i] = gw[g];
+        s[1][i] = blk[j];
+        s[2][i] = blk[(size_t)stride + j];
+        s[3][i] = blk[2 * (size_t)stride + j];
+    }
+}
+// wave q < 5 of the workgroup: its quantity's sum over the staged tile -> part[q * nt + t]
+__device__ __forceinline__ void est_moments(const float (*s)[PF_SUM_TILE], int cnt, float *part, int nt, int t)
+{
+    const int q = threadIdx.x >> 6;
+    if (q >= 5) return;
+    const float *p = s[q < 2 ? 0 : q - 1];
+    const float v = q == 0 ? wave_sum_canonical(cnt, [&](int i) { return s[0][i]; })
+                           : wave_sum_canonical(cnt, [&](int i) { return s[0][i] * p[i]; });
+    if ((threadIdx.x & 63) == 0) part[q * nt + t] = v;
+}
+// S0 and the three means from pass A's tile sums: the canonical sum gives every wave of every workgroup the same bits
+__device__ __forceinline__ void est_means(const float *part, int nt, float *s0, float m[3])
+{
+    *s0 = wave_sum_canonical(nt, [&](int i) { return part[i]; });
+    for (int k = 0; k < 3; k++) m[k] = pf::fdiv(wave_sum_canonical(nt, [&](int i) { return part[(2 + k) * nt + i]; }), *s0);
+}
+// the staged poses become deviations d = p - m (each element once), then wave q: sum of (w * d_k) * d_l -> cen[q * nt + t]
+__device__ __forceinline__ void est_centred(float (*s)[PF_SUM_TILE], int cnt, const float m[3], float *cen, int nt, int t)
+{
+    for (int i = threadIdx.x; i < cnt; i += PF_EST_WAVES * 64) {
+        s[1][i] = s[1][i] - m[0];
+        s[2][i] = s[2][i] - m[1];
+        s[3][i] = s[3][i] - m[2];
+    }
+    __syncthreads();
+    const int q = threadIdx.x >> 6; // xx, xy, xtheta, yy, ytheta, thetatheta
+    const int k = q < 3 ? 0 : (q < 5 ? 1 : 2), l = q < 3 ? q : (q < 5 ? q - 2 : 2);
+    const float *dk = s[1 + k], *dl = s[1 + l];
+    const float v = wave_sum_canonical(cnt, [&](int i) { return (s[0][i] * dk[i]) * dl[i]; });
+    if ((threadIdx.x & 63) == 0) cen[q * nt + t] = v;
+}
+// the 16 output floats from the tile sums (first wave of the workgroup)
+__device__ __forceinline__ void est_finish(const float *part, int nt, int gn, float *out)
+{
+    if (threadIdx.x >= 64) return;
+    float s0, m[3], c[6];
+    est_means(part, nt, &s0, m);
+    const float s2 = wave_sum_canonical(nt, [&](int i) { return part[nt + i]; });
+    for (int q = 0; q < 6; q++) c[q] = pf::fdiv(wave_sum_canonical(nt, [&](int i) { return part[(5 + q) * nt + i]; }), s0);
+    if (threadIdx.x != 0) return;
+    for (int k = 0; k < 3; k++) out[k] = m[k];
+    for (int q = 0; q < 6; q++) out[3 + q] = c[q];
+    out[9] = pf::fdiv(s0 * s0, s2);
+    out[10] = s0;
+    out[11] = s2;
+    out[12] = (float)gn;
+    out[13] = out[14] = out[15] = 0.0f;
+}
+__global__ __launch_bounds__(PF_EST_WAVES * 64) void k_estimate_moments(const float *__restrict__ gw, const float *__restrict__ gpose,
+                                                                        int stride, int gn, float *__restrict__ part, int nt)
+{
+    __shared__ float s[4][PF_SUM_TILE];
+    const int t = blockIdx.x, cnt = min(PF_SUM_TILE, gn - t * PF_SUM_TILE);
+    est_stage(s, gw, gpose, stride, t * PF_SUM_TILE, cnt);
+    __syncthreads();
+    est_moments(s, cnt, part, nt, t);
+}
+// pass A's sums are complete (stream order): `mom` = part[0 .. 5 nt) is read-only here, `cen` = part + 5 nt is written
+__global__ __launch_bounds__(PF_EST_WAVES * 64) void k_estimate_centred(const float *__restrict__ gw, const float *__restrict__ gpose,
+                                                                        int stride, int gn, const float *__restrict__ mom,
+                                                                        float *__restrict__ cen, int nt)
+{
+    __shared__ float s[4][PF_SUM_TILE];
+    const int t = blockIdx.x, cnt = min(PF_SUM_TILE, gn - t * PF_SUM_TILE);
+    est_stage(s, gw, gpose, stride, t * PF_SUM_TILE, cnt);
+    float s0, m[3];
+    est_means(mom, nt, &s0, m);
+    __syncthreads();
+    est_centred(s, cnt, m, cen, nt, t);
+}
+__global__ __launch_bounds__(64) void k_estimate_final(const float *__restrict__ part, int nt, int gn, float *__restrict__ out)
+{
+    est_finish(part, nt, gn, out);
+}
+// up to one tile: the three passes as one workgroup.  The tile sums cross from wave to wave through `part` in global memory, a barrier
+// between writer and readers (not __restrict__: the loads must not be taken for loads of kernel-invariant memory).
+__global__ __launch_bounds__(PF_EST_WAVES * 64) void k_estimate_small(const float *gw, const float *gpose, int stride, int gn, float *part,
+                                                                      float *out)
+{
+    __shared__ float s[4][PF_SUM_TILE];
+    est_stage(s, gw, gpose, stride, 0, gn);
+    __syncthreads();
+    est_moments(s, gn, part, 1, 0);
+    __syncthreads();
+    float s0, m[3];
+    est_means(part, 1, &s0, m);
+    est_centred(s, gn, m, part + 5, 1, 0);
+    __syncthreads();
+    est_finish(part, 1, gn, out);
+}
+
+extern "C" int pfslam_estimate(pfslam_handle *h, float out[16])
+{
+    if (!h || !out) return fail("pfslam_estimate: bad argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    CHK(settle(h));
+    if (!h->est_part) return fail("pfslam_estimate: more than 4096 * 4096 particles (the tile sums of the canonical sum must fit one tile)");
+    const int gn = h->gn, nt = (gn + PF_SUM_TILE - 1) / PF_SUM_TILE;
+    float *part = h->est_part, *res = h->est_part + (size_t)11 * nt;
+    const dim3 wg(PF_EST_WAVES * 64);
+    if (nt == 1) {
+        hipLaunchKernelGGL(k_estimate_small, dim3(1), wg, 0, h->stream, (const float *)h->gw, (const float *)h->gpose, h->stride, gn, part, res);
+    } else {
+        hipLaunchKernelGGL(k_estimate_moments, dim3(nt), wg, 0, h->stream, (const float *)h->gw, (const float *)h->gpose, h->stride, gn, part, nt);
+        hipLaunchKernelGGL(k_estimate_centred, dim3(nt), wg, 0, h->stream, (const float *)h->gw, (const float *)h->gpose, h->stride, gn,
+                           (const float *)part, part + (size_t)5 * nt, nt);
+        hipLaunchKernelGGL(k_estimate_final, dim3(1), dim3(64), 0, h->stream, (const float *)part, nt, gn, res);
+    }
+    HIPCHK(hipGetLastError());
+    float r[16];
+    HIPCHK(hipMemcpyAsync(r, res, sizeof(r), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (!(r[10] > 0.0f) || !std::isfinite(r[10])) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "pfslam_estimate: the weights sum to %g (it must be finite and > 0): no mean, no covariance", (double)r[10]);
+        return fail(msg);
+    }
+    memcpy(out, r, sizeof(r));
+    return 0;
+}
+
 // ---- 2-D grid path -------------------------------------------------------------------------
 extern "C" int pfslam_set_grid(pfslam_handle *h, const int8_t *grid, int dimx, int dimy)
 {

@@ -243,6 +243,22 @@ void pfslamSetResampler(int mode)
     g_resampler = mode;
     if (g_handle) PFCHK(pfslam_set_resampler(g_handle, mode), "pfslamSetResampler");
 }
+bool pfslamPoseEstimate(glm::vec3 &mean, float cov[9], float *neff)
+{
+    if (!g_handle) return false;
+    float e[16];
+    if (pfslam_estimate(g_handle, e)) { // (a cloud whose weights sum to zero has no mean: a state of the filter, not a failure of the program)
+        fprintf(stderr, "pfslamPoseEstimate: %s\n", pfslam_last_error());
+        return false;
+    }
+    mean = glm::vec3(e[0], e[1], e[2]);
+    if (cov) {
+        const float c[9] = {e[3], e[4], e[5], e[4], e[6], e[7], e[5], e[7], e[8]};
+        memcpy(cov, c, sizeof(c));
+    }
+    if (neff) *neff = e[9];
+    return true;
+}
 std::vector<std::pair<int, int>> pfslamLoopClosures()
 {
     std::vector<std::pair<int, int>> out;

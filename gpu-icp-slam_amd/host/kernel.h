@@ -57,6 +57,11 @@ std::vector<std::pair<int, int>> pfslamLoopClosures();
 // whatever the particle count (default), 1 = one multinomial draw per particle, 2 = systematic resampling.  Read by the next
 // particleFilterInit (a live filter takes it from its next frame); a mode outside 0..2 prints and exits like every other error.
 void pfslamSetResampler(int mode);
+// Posterior of the live filter (no reference counterpart; include/pfslam.h, pfslam_estimate): weighted mean pose (x, y, heading -- a LINEAR
+// mean: the filter never wraps headings), row-major symmetric 3x3 covariance and Neff, reduced on the device; like getPCData it first waits
+// for the frames in flight.  cov and neff may be null.  false (and a line on stderr): no live filter, or the weights do not sum to a
+// positive finite number; the outputs are then untouched.
+bool pfslamPoseEstimate(glm::vec3 &mean, float cov[9], float *neff);
 // Map export for an end-to-end comparison: the point-cloud map as the reference's viewer filters it
 // (nodes with w > -100, main.cpp:269-284) -> PREFIX.kd.bin (float x, y, z, w per point, in node order) + PREFIX.kd.csv, and
 // the 2-D occupancy grid -> PREFIX.grid.i8 (dim.x * dim.y signed bytes, cell (x, y) at x * dim.x + y) + PREFIX.grid.pgm

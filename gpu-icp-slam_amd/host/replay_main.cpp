@@ -1,9 +1,11 @@
 // replay_main.cpp -- headless counterpart of the reference's main loop (main.cpp:47-96, 175-229):
-//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [export=PREFIX]
+//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [export=PREFIX]
 //     grid           the 2-D occupancy-grid stages instead of the point-cloud ones
 //     loop           UpdateTopology + CheckLoopClosure at the end of every frame (kernel.cu:1750-1751, commented out in
 //                    the reference's shipped step); loop-closure proposals are printed per frame
 //     resampler=N    PFResample's draw (pfslamSetResampler): 0 the reference's seeding (default), 1 per-particle seeds, 2 systematic
+//     estimate=1     a second line per frame: the cloud's weighted mean pose, the six covariance entries (xx xy xt yy yt tt) and Neff
+//                    (pfslamPoseEstimate), as decimals and as float bits
 //     export=PREFIX  after the last frame: the map as the reference's viewer filters it (KD nodes with w > -100,
 //                    main.cpp:269-284) and the occupancy grid -> PREFIX.kd.bin / .kd.csv / .grid.i8 / .grid.pgm
 // iteration 0: Free + Init; then particleFilter(pbo=NULL, ++iteration, lidar) until the scans run out.
@@ -18,18 +20,19 @@
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [export=PREFIX]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [export=PREFIX]\n", argv[0]);
         return 1;
     }
     Scene *scene = new Scene(argv[1]);
     Lidar *lidar = new Lidar(argv[2]);
     size_t last = lidar->scans.size() - 1;
-    bool loop = false;
+    bool loop = false, estimate = false;
     std::string export_prefix;
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "grid") == 0) pfslamUseGridMap(true);
         else if (strcmp(argv[i], "loop") == 0) loop = true;
         else if (strncmp(argv[i], "resampler=", 10) == 0) pfslamSetResampler(atoi(argv[i] + 10));
+        else if (strncmp(argv[i], "estimate=", 9) == 0) estimate = atoi(argv[i] + 9) != 0;
         else if (strncmp(argv[i], "export=", 7) == 0) export_prefix = argv[i] + 7;
         else if (atoi(argv[i]) > 0) last = std::min(last, (size_t)atoi(argv[i]));
     }
@@ -55,6 +58,23 @@ int main(int argc, char **argv)
             for (size_t k = 0; k < pairs.size() && k < 8; k++) printf(" (%d,%d)", pairs[k].first, pairs[k].second);
         }
         printf("\n");
+        if (estimate) {
+            glm::vec3 m;
+            float c[9], neff = 0.0f;
+            if (pfslamPoseEstimate(m, c, &neff)) {
+                const float v[10] = {m.x, m.y, m.z, c[0], c[1], c[2], c[4], c[5], c[8], neff};
+                printf("estimate %zu mean %.6f %.6f %.6f cov %.6e %.6e %.6e %.6e %.6e %.6e neff %.3f bits", iteration, v[0], v[1], v[2], v[3], v[4], v[5],
+                       v[6], v[7], v[8], v[9]);
+                for (int k = 0; k < 10; k++) {
+                    unsigned int b;
+                    memcpy(&b, &v[k], 4);
+                    printf(" %08x", b);
+                }
+                printf("\n");
+            } else {
+                printf("estimate %zu none\n", iteration);
+            }
+        }
     }
     printf("mean step+readback %.3f ms over %zu frames\n", iteration ? total_ms / iteration : 0.0, iteration);
     if (loop) printf("loop-closure proposals %zu\n", proposals);

@@ -149,6 +149,21 @@ class ShardedSlam:
         self.eng.set_particles(np.ascontiguousarray(p_global[self.goff:self.goff + self.n]))
     def particles(self): return self.eng.particles()   # this rank's shard
 
+    def estimate(self):
+        """Mean pose, covariance and Neff of the WHOLE cloud (pfslam_estimate), the same bits on every rank and for any number of ranks:
+        the frames in flight are booked, the weights (5 -> 10) and the pose blocks (16 -> 17) all-gathered on the handle's stream, and the
+        engine reduces the gathered arrays.  Every rank calls it; world 1 issues no collective."""
+        self.eng.synchronize()
+        if self.world > 1:
+            if self.dist is None or self.buf is None:
+                raise RuntimeError("ShardedSlam.estimate needs torch.distributed and the handle's device buffers to gather the cloud")
+            issued = self.collectives
+            local, glob = self.buf.pose_blocks()
+            self._all_gather(self.buf.gw, self.buf.w, 2)
+            self._all_gather(glob, local, 0)
+            self.collectives = issued                   # (the count is the frames' fixed schedule)
+        return self.eng.estimate()
+
     def _all_gather(self, dst, src, which):
         """Collective `which` (0 pose blocks, 1 keys, 2 weights) of the frame being enqueued, in the stream the engine names for it
         (GPU engines: pfslam_shard_stream -- stream order is all the ordering there is; gloo completes it before it returns)."""

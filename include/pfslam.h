@@ -337,6 +337,30 @@ int pfslam_set_trig(pfslam_handle *h, int devlib);
  * rank must set the same mode (the caller's duty: nothing checks it); the draw depends on global quantities only, so results then stay
  * bit-identical for any number of ranks. */
 int pfslam_set_resampler(pfslam_handle *h, int mode);
+/* Posterior estimate (no reference counterpart): weighted mean pose, 3x3 covariance and Neff of the whole cloud, reduced on the device.
+ * Reads state, writes none.  With gn the global particle count, (x_i, y_i, theta_i, w_i) the particle with GLOBAL index i, p_k one of
+ * x, y, theta, and csum the canonical sum (64 lanes, lane l adds elements l, l + 64, ... in ascending order, then an xor butterfly 32 .. 1;
+ * above 4096 elements the 4096-element tiles are summed that way, then the tile sums the same way), all in float, one rounding per
+ * operation, in the order written (no contraction; divisions correctly rounded):
+ *     S0    = csum(w_i)                          S2 = csum(w_i * w_i)
+ *     m_k   = csum(w_i * p_k,i) / S0             k = x, y, theta
+ *     d_k,i = p_k,i - m_k
+ *     C_kl  = csum((w_i * d_k,i) * d_l,i) / S0   (k, l) = xx, xy, xtheta, yy, ytheta, thetatheta
+ *     Neff  = (S0 * S0) / S2
+ *   out[0..2] = m, out[3..8] = C in the order above, out[9] = Neff, out[10] = S0, out[11] = S2, out[12] = (float)gn, out[13..15] = 0.
+ * Two passes -- the means, then the centred moments: sum(w x^2) - m^2 would cancel (x is tens of metres, the cloud's sigma centimetres).
+ * Scaling every weight by a power of two leaves m, C and Neff bit-identical.
+ * Heading: the mean is LINEAR on purpose.  Nothing in the filter wraps theta -- dispersion, ICP and pfslam_shift_particles only add -- so a
+ * cloud's headings are a contiguous set of reals and their linear mean and spread are the cloud's.  A caller who uploads headings wrapped
+ * into (-pi, pi] through pfslam_set_particles, with a cloud that straddles the cut, gets a meaningless theta row and column.
+ * Refused (non-zero, pfslam_last_error names the cause, out untouched): S0 not finite or not > 0; gn above 4096 * 4096.
+ * Like every entry point but the step functions the call first books the frames in flight, then runs on the handle's stream: it describes
+ * exactly the arrays pfslam_get_particles would return at that moment -- after a frame that resampled, the resampled cloud with w = 1.
+ * Sharded handles (global_n > n_particles) read the caller's gathered buffers, like pfslam_resample_plan: buffer 10, the global weights, and
+ * buffer 17, the global pose blocks -- the caller must have all-gathered both from buffers 5 and 16 after the last frame.  The sums run in
+ * global index order (tile edges at multiples of 4096 of the GLOBAL index), so every rank's result is bit-identical for any number of ranks
+ * and equals the unsharded handle's.  Unsharded handles read their own arrays (10 and 17 alias 5 and 16). */
+int pfslam_estimate(pfslam_handle *h, float out[16]);
 /* ---- round-5 frame loop: test and measurement support (no reference counterpart) ----
  * pfslam_set_serial(h, 1): every launch of every frame on ONE stream, in the order the four chains of a frame are enqueued (what the
  * environment variable PFSLAM_SERIAL=1 sets at creation).  Results and the cell rows' bookkeeping are the same as with the chains on their
