@@ -1624,9 +1624,10 @@ static int plan_min_particles()
     static const int v = getenv("PFSLAM_PLAN_MIN_N") ? atoi(getenv("PFSLAM_PLAN_MIN_N")) : 4608;
     return v;
 }
-// frame_loop: the round-5 frame of pfslam_step -- nothing on its chain waits for the marking pass or the walks of new cells, so the rows pay
-// from a few waves of particles on (1000 particles: 0.160 -> 0.144 ms per frame, 3000: 0.229 -> 0.177); everywhere else (stage-level calls,
-// the sharded frame: synchronous or same-frame passes) they start at ~4.6 k particles
+// frame_loop: the round-5 frame of pfslam_step and of the sharded calls (frame_choice -> frame_v2_ok, per shard: a shard of 65 particles
+// takes them) -- nothing on its chain waits for the marking pass or the walks of new cells, so the rows pay from a few waves of
+// particles on (1000 particles: 0.160 -> 0.144 ms per frame, 3000: 0.229 -> 0.177); everywhere else (stage-level calls, the staged
+// chain a frame falls back to, sharded or not: synchronous or same-frame passes) they start at ~4.6 k particles
 static bool org_use_cells(const pfslam_handle *h, bool *use_plan, bool frame_loop = false)
 {
     static const bool env_min = getenv("PFSLAM_PLAN_MIN_N") != nullptr;

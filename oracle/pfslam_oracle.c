@@ -1057,6 +1057,26 @@ void orc_weighted_sample_indices(const float *cdf, int n, float neff, int frame,
     }
 }
 
+/* The same source indices as the loop above, which stays the definition.  orc_engine_seed shifts thread i into bits 22 .. 31 of a
+ * 32-bit key whose bit 31 is always set, so thread i's seed -- and with it its draw and its search -- depends on i & 511 only (H5):
+ * at most 512 searches are distinct, each is done once by the loop above and copied to the threads that share it.  Exact for every
+ * input (a non-monotone cdf included: the search itself is the loop's); tests/test_resampler_spec.py holds the two equal. */
+void orc_weighted_sample_indices_memo(const float *cdf, int n, float neff, int frame, int i0, int count,
+                                      int32_t *src_idx)
+{
+    int32_t memo[512];
+    unsigned char have[512];
+    memset(have, 0, sizeof(have));
+    for (int k = 0; k < count; k++) {
+        int i = i0 + k, slot = i & 511;
+        if (!have[slot]) {
+            orc_weighted_sample_indices(cdf, n, neff, frame, i, 1, &memo[slot]);
+            have[slot] = 1;
+        }
+        src_idx[k] = memo[slot];
+    }
+}
+
 int orc_resample(orc_particle *p, int n, int frame, float *neff_out, int32_t *src_idx)
 {
     float *w = (float *)calloc((size_t)(n > 0 ? n : 1), sizeof(float));
@@ -1072,7 +1092,7 @@ int orc_resample(orc_particle *p, int n, int frame, float *neff_out, int32_t *sr
         int32_t *src = (int32_t *)malloc(sizeof(int32_t) * (size_t)n);
         orc_particle *snap = (orc_particle *)malloc(sizeof(orc_particle) * (size_t)n);
         orc_inclusive_scan_f32(w, n, cdf);
-        orc_weighted_sample_indices(cdf, n, Neff, frame, 0, n, src);
+        orc_weighted_sample_indices_memo(cdf, n, Neff, frame, 0, n, src);
         memcpy(snap, p, sizeof(orc_particle) * (size_t)n); /* H3: gather from a snapshot */
         for (int i = 0; i < n; i++) {
             p[i] = snap[src[i]];

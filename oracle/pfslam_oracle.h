@@ -136,6 +136,9 @@ void orc_kd_balance(orc_node *list, int n);
 int orc_resample(orc_particle *p, int n, int frame, float *neff_out, int32_t *src_idx);
 void orc_weighted_sample_indices(const float *cdf, int n, float neff, int frame, int i0, int count,
                                  int32_t *src_idx);
+/* the same indices, every distinct search done once (thread i's draw depends on i & 511 only, H5); orc_resample uses it */
+void orc_weighted_sample_indices_memo(const float *cdf, int n, float neff, int frame, int i0, int count,
+                                      int32_t *src_idx);
 
 /* ---- A17/A18: 2-D occupancy grid path (kernel.cu:243-372, 513-621) ---- */
 void orc_score_grid(const int8_t *grid, int dimx, int dimy, const orc_patch *patch,

@@ -89,6 +89,8 @@ def lib():
     L.orc_resample.restype = i32; L.orc_resample.argtypes = [vp, i32, i32, vp, vp]
     L.orc_weighted_sample_indices.restype = None
     L.orc_weighted_sample_indices.argtypes = [vp, i32, f32, i32, i32, i32, vp]
+    L.orc_weighted_sample_indices_memo.restype = None
+    L.orc_weighted_sample_indices_memo.argtypes = [vp, i32, f32, i32, i32, i32, vp]
     L.orc_score_grid.restype = None; L.orc_score_grid.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp]
     L.orc_update_map_grid.restype = None; L.orc_update_map_grid.argtypes = [vp, i32, i32, vp, vp, vp, i32]
     L.orc_topology_init.restype = None; L.orc_topology_init.argtypes = [vp]

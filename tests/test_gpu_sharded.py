@@ -174,10 +174,16 @@ class _VirtualRanks:
     """`world` sharded handles on one GPU stepped as ONE engine: the three all-gathers of the frame done by hand on the zero-copy
     views (the protocol of ShardedSlam.step), every rank's pose / trace / closures / graph checked against rank 0's."""
 
-    def __init__(self, pkg, torch, n_global, world, **kw):
+    def __init__(self, pkg, torch, n_global, world, stride=None, **kw):
+        """stride: an explicit shard stride instead of shard_layout's ceil(n_global / world) -- include/pfslam.h allows any stride whose
+        last shard is shorter and not empty (`world` must then be the number of shards that stride gives)."""
         sharded = importlib.import_module("gpu-icp-slam_amd.sharded")
         self.torch, self.n_global = torch, n_global
-        self.lay = [sharded.shard_layout(n_global, world, r) for r in range(world)]
+        if stride is None:
+            self.lay = [sharded.shard_layout(n_global, world, r) for r in range(world)]
+        else:
+            assert (n_global + stride - 1) // stride == world, (n_global, world, stride)
+            self.lay = [(stride, r * stride, min(stride, n_global - r * stride)) for r in range(world)]
         self.engs = [pkg.PfSlam(cnt, global_offset=off, global_n=n_global, shard_stride=stride, **kw) for stride, off, cnt in self.lay]
         self.bufs = [sharded.GpuBuffers(e, torch, 0) for e in self.engs]
 

@@ -110,3 +110,25 @@ def test_binding_and_library_export_the_entry_point(pkg):
     assert "pfslam_set_resampler" in pkg.binding.SYMBOLS
     assert hasattr(pkg.load(), "pfslam_set_resampler")
     assert hasattr(pkg.PfSlam, "set_resampler")
+
+
+def _memo_inputs():
+    for name, make, frame in CASES:
+        yield name, make()["w"], frame
+    for n in (513, 1025, 40000):
+        yield "random%d" % n, np.random.RandomState(7 * n).uniform(0, 1, n).astype(np.float32) ** 8, FRAME
+
+
+@pytest.mark.parametrize("name,w,frame", list(_memo_inputs()), ids=[c[0] for c in _memo_inputs()])
+def test_memoised_sampling_equals_the_loop(name, w, frame):
+    """orc_weighted_sample_indices_memo (what orc_resample calls: one search per distinct i & 511) against orc_weighted_sample_indices,
+    the definition: every source index of the whole array, and of a slice that starts off a multiple of 512 (a shard's)."""
+    L = O.lib()
+    neff, cdf = R.sums_and_cdf(w)
+    n = len(cdf)
+    for i0, count in ((0, n), (n // 3 + 1, n - (n // 3 + 1))):
+        want, got = np.full(count, -1, np.int32), np.full(count, -2, np.int32)
+        L.orc_weighted_sample_indices(O.P(cdf), n, float(neff), frame, i0, count, O.P(want))
+        L.orc_weighted_sample_indices_memo(O.P(cdf), n, float(neff), frame, i0, count, O.P(got))
+        assert (got == want).all(), "%s, i0 %d: %d of %d sources differ" % (name, i0, (got != want).sum(), count)
+    assert n <= 512 or len(np.unique(want)) <= 512
