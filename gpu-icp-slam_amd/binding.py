@@ -26,6 +26,7 @@ SYMBOLS = [
     "pfslam_kd_create", "pfslam_kd_insert_list", "pfslam_kd_insert_node", "pfslam_kd_balance", "pfslam_set_timing", "pfslam_get_timers", "pfslam_resample_plan", "pfslam_resample_gather", "pfslam_maybe_balance", "pfslam_kd_size", "pfslam_topology_update", "pfslam_find_walls",
     "pfslam_check_loop_closure", "pfslam_get_topology", "pfslam_set_topology", "pfslam_get_closures", "pfslam_score_census", "pfslam_set_census", "pfslam_get_census_log", "pfslam_ubench_gather", "pfslam_plan_stats", "pfslam_cell_stats", "pfslam_kd_parallel_sort", "pfslam_kd_sort_threads", "pfslam_kd_whole_node",
     "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_estimate", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
+    "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
 
@@ -38,6 +39,15 @@ class Config(C.Structure):
                 ("strict_host_mirror", C.c_int32), ("free_upload_bug", C.c_int32),
                 ("balance_period", C.c_int32), ("global_offset", C.c_int32), ("global_n", C.c_int32),
                 ("shard_stride", C.c_int32), ("reserved_", C.c_int32 * 2)]
+
+
+class RegisterOpts(C.Structure):
+    """pfslam_register_opts (include/pfslam.h)."""
+    _fields_ = [("max_iters", C.c_int32), ("match", C.c_int32), ("select", C.c_int32), ("update", C.c_int32),
+                ("max_dist", C.c_float), ("eps_xy", C.c_float), ("eps_theta", C.c_float), ("min_pairs", C.c_int32)]
+
+
+REGISTER_STATUS = {0: "max_iters", 1: "converged", 2: "too_few_pairs", 3: "not_finite"}
 
 
 class PfSlamError(RuntimeError):
@@ -141,6 +151,10 @@ def load():
     L.pfslam_set_trig.argtypes = [vp, i32]
     L.pfslam_set_resampler.argtypes = [vp, i32]
     L.pfslam_estimate.argtypes = [vp, vp]
+    L.pfslam_register_default_opts.restype = None
+    L.pfslam_register_default_opts.argtypes = [vp]
+    L.pfslam_nearest.argtypes = [vp, vp, i32, vp, vp]
+    L.pfslam_register.argtypes = [vp, vp, vp, vp, vp, vp]
     L.pfslam_debug_check_cells.argtypes = [vp, vp]
     L.pfslam_set_probe.argtypes = [vp, i32]
     L.pfslam_get_probe.argtypes = [vp, vp, i32, vp, vp]
@@ -536,6 +550,34 @@ class PfSlam:
         """Weighted mean pose, 3x3 covariance and Neff of the cloud, reduced on the device (include/pfslam.h, pfslam_estimate): the heading
         mean is linear.  Sharded handles: buffers 10 and 17 must hold the gathered weights and pose blocks (ShardedSlam.estimate does that)."""
         return estimate_dict(self.estimate_raw())
+
+    def nearest(self, xyz):
+        """Exact nearest map node of every query point (include/pfslam.h, pfslam_nearest): (index, squared distance); index -1 for a
+        query with a non-finite coordinate."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        best = np.empty(len(xyz), np.int32)
+        d2 = np.empty(len(xyz), np.float32)
+        _chk(self.L.pfslam_nearest(self._h, _p(xyz), len(xyz), _p(best), _p(d2)), "pfslam_nearest")
+        return best, d2
+
+    def register(self, start=None, **opts):
+        """Iterated scan-to-map ICP on the device (include/pfslam.h, pfslam_register) from `start` (None: the handle's pose).  Options by
+        name (max_iters, match, select, update, max_dist, eps_xy, eps_theta, min_pairs) over pfslam_register_default_opts.  Returns pose,
+        status (0 max_iters, 1 converged, 2 too few pairs, 3 not finite), iterations, pairs, residual and trace (iterations x 8:
+        x', y', theta', their three increments, pairs, mean squared residual).  Reads the handle's state, writes none of it."""
+        o = RegisterOpts()
+        self.L.pfslam_register_default_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in dict(RegisterOpts._fields_):
+                raise TypeError("register() has no option %r" % k)
+            setattr(o, k, v)
+        pose, info = np.zeros(3, np.float32), np.zeros(8, np.float32)
+        trace = np.zeros((max(1, min(int(o.max_iters), 64)), 8), np.float32)
+        st = None if start is None else np.ascontiguousarray(start, dtype=np.float32)
+        _chk(self.L.pfslam_register(self._h, None if st is None else _p(st), C.byref(o), _p(pose), _p(info), _p(trace)), "pfslam_register")
+        it = int(info[1])
+        return {"pose": pose, "status": int(info[0]), "iterations": it, "pairs": int(info[2]), "residual": float(info[3]),
+                "trace": trace[:it].copy()}
 
     def frame_mode(self):
         out = (C.c_int * 4)()

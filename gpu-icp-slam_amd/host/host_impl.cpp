@@ -259,6 +259,23 @@ bool pfslamPoseEstimate(glm::vec3 &mean, float cov[9], float *neff)
     if (neff) *neff = e[9];
     return true;
 }
+bool pfslamRegister(glm::vec3 start, int max_iters, glm::vec3 &pose, int *status, int *iterations)
+{
+    if (!g_handle) return false;
+    pfslam_register_opts o;
+    pfslam_register_default_opts(&o);
+    if (max_iters > 0) o.max_iters = max_iters;
+    const float s[3] = {start.x, start.y, start.z};
+    float p[3], info[8];
+    if (pfslam_register(g_handle, s, &o, p, info, nullptr)) { // (an empty map is a state of the filter, not a failure of the program)
+        fprintf(stderr, "pfslamRegister: %s\n", pfslam_last_error());
+        return false;
+    }
+    pose = glm::vec3(p[0], p[1], p[2]);
+    if (status) *status = (int)info[0];
+    if (iterations) *iterations = (int)info[1];
+    return true;
+}
 std::vector<std::pair<int, int>> pfslamLoopClosures()
 {
     std::vector<std::pair<int, int>> out;

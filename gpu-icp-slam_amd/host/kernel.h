@@ -62,6 +62,12 @@ void pfslamSetResampler(int mode);
 // for the frames in flight.  cov and neff may be null.  false (and a line on stderr): no live filter, or the weights do not sum to a
 // positive finite number; the outputs are then untouched.
 bool pfslamPoseEstimate(glm::vec3 &mean, float cov[9], float *neff);
+// Scan-to-map registration of the live filter's scan against its map (no reference counterpart; include/pfslam.h, pfslam_register): up to
+// max_iters ICP iterations on the device from `start`, with exact nearest neighbours, the rejected beams left out, a 0.5 m gate and the
+// rigid update (pfslam_register_default_opts; max_iters <= 0 keeps its 40).  Reads the filter, changes nothing in it; like getPCData it
+// first waits for the frames in flight.  status: 0 max_iters done, 1 converged, 2 too few pairs, 3 not finite; iterations may be null.
+// false (and a line on stderr): no live filter, no map yet, or an option out of range; the outputs are then untouched.
+bool pfslamRegister(glm::vec3 start, int max_iters, glm::vec3 &pose, int *status, int *iterations);
 // Map export for an end-to-end comparison: the point-cloud map as the reference's viewer filters it
 // (nodes with w > -100, main.cpp:269-284) -> PREFIX.kd.bin (float x, y, z, w per point, in node order) + PREFIX.kd.csv, and
 // the 2-D occupancy grid -> PREFIX.grid.i8 (dim.x * dim.y signed bytes, cell (x, y) at x * dim.x + y) + PREFIX.grid.pgm

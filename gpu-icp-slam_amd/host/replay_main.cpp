@@ -1,11 +1,13 @@
 // replay_main.cpp -- headless counterpart of the reference's main loop (main.cpp:47-96, 175-229):
-//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [export=PREFIX]
+//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [export=PREFIX]
 //     grid           the 2-D occupancy-grid stages instead of the point-cloud ones
 //     loop           UpdateTopology + CheckLoopClosure at the end of every frame (kernel.cu:1750-1751, commented out in
 //                    the reference's shipped step); loop-closure proposals are printed per frame
 //     resampler=N    PFResample's draw (pfslamSetResampler): 0 the reference's seeding (default), 1 per-particle seeds, 2 systematic
 //     estimate=1     a second line per frame: the cloud's weighted mean pose, the six covariance entries (xx xy xt yy yt tt) and Neff
 //                    (pfslamPoseEstimate), as decimals and as float bits
+//     register=K     a further line per frame: the pose pfslamRegister reaches from the frame's pose in at most K iterations (the frame's scan
+//                    against the frame's map; the filter is not changed), its status and iteration count, as decimals and as float bits
 //     export=PREFIX  after the last frame: the map as the reference's viewer filters it (KD nodes with w > -100,
 //                    main.cpp:269-284) and the occupancy grid -> PREFIX.kd.bin / .kd.csv / .grid.i8 / .grid.pgm
 // iteration 0: Free + Init; then particleFilter(pbo=NULL, ++iteration, lidar) until the scans run out.
@@ -20,19 +22,21 @@
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [export=PREFIX]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [export=PREFIX]\n", argv[0]);
         return 1;
     }
     Scene *scene = new Scene(argv[1]);
     Lidar *lidar = new Lidar(argv[2]);
     size_t last = lidar->scans.size() - 1;
     bool loop = false, estimate = false;
+    int register_iters = 0;
     std::string export_prefix;
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "grid") == 0) pfslamUseGridMap(true);
         else if (strcmp(argv[i], "loop") == 0) loop = true;
         else if (strncmp(argv[i], "resampler=", 10) == 0) pfslamSetResampler(atoi(argv[i] + 10));
         else if (strncmp(argv[i], "estimate=", 9) == 0) estimate = atoi(argv[i] + 9) != 0;
+        else if (strncmp(argv[i], "register=", 9) == 0) register_iters = atoi(argv[i] + 9);
         else if (strncmp(argv[i], "export=", 7) == 0) export_prefix = argv[i] + 7;
         else if (atoi(argv[i]) > 0) last = std::min(last, (size_t)atoi(argv[i]));
     }
@@ -73,6 +77,17 @@ int main(int argc, char **argv)
                 printf("\n");
             } else {
                 printf("estimate %zu none\n", iteration);
+            }
+        }
+        if (register_iters > 0) {
+            glm::vec3 r;
+            int status = 0, iters = 0;
+            if (pfslamRegister(pos, register_iters, r, &status, &iters)) {
+                unsigned int b[3];
+                memcpy(&b[0], &r.x, 4); memcpy(&b[1], &r.y, 4); memcpy(&b[2], &r.z, 4);
+                printf("register %zu pose %.6f %.6f %.6f status %d iterations %d bits %08x %08x %08x\n", iteration, r.x, r.y, r.z, status, iters, b[0], b[1], b[2]);
+            } else {
+                printf("register %zu none\n", iteration);
             }
         }
     }

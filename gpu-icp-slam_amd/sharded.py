@@ -164,6 +164,11 @@ class ShardedSlam:
             self.collectives = issued                   # (the count is the frames' fixed schedule)
         return self.eng.estimate()
 
+    def register(self, start=None, **opts):
+        """Iterated scan-to-map ICP (pfslam_register): the map and the scan are replicated, so the call goes to this rank's handle as it
+        is -- no collective -- and returns the unsharded handle's bits on every rank."""
+        return self.eng.register(start, **opts)
+
     def _all_gather(self, dst, src, which):
         """Collective `which` (0 pose blocks, 1 keys, 2 weights) of the frame being enqueued, in the stream the engine names for it
         (GPU engines: pfslam_shard_stream -- stream order is all the ordering there is; gloo completes it before it returns)."""

@@ -26,6 +26,8 @@
  *   pfslam_step_grid                   the frame loop of kernel.cu:1702-1762 with the 2-D stages
  *                                      PFMeasurementUpdate / PFUpdateMap  kernel.cu:307-339, 551-577
  *   pfslam_traverse                    findCorrespondenceIndexKD          kernel.cu:924-972
+ *   pfslam_nearest / pfslam_register   no counterpart: the exact nearest map node, and transformPointICP iterated on the device with
+ *                                      its three defects optional (see pfslam_register below)
  *   pfslam_topology_update, find_walls,
  *   check_loop_closure, get_topology   UpdateTopology / FindWalls / CheckLoopClosure   kernel.cu:623-795
  *   pfslam_shard_disperse / score / weights / finish   particleFilter split where a multi-GPU caller places its three
@@ -361,6 +363,70 @@ int pfslam_set_resampler(pfslam_handle *h, int mode);
  * global index order (tile edges at multiples of 4096 of the GLOBAL index), so every rank's result is bit-identical for any number of ranks
  * and equals the unsharded handle's.  Unsharded handles read their own arrays (10 and 17 alias 5 and 16). */
 int pfslam_estimate(pfslam_handle *h, float out[16]);
+/* ---- scan-to-map registration (no reference counterpart) ----
+ * pfslam_icp restates the reference's transformPointICP bit for bit: ONE step, with three properties that keep a caller from iterating it
+ * into a scan matcher (measured with the CPU oracle on a 4000-point synthetic map, 1081 beams):
+ *   1. its correspondences are not nearest neighbours: findCorrespondenceIndexKD (pfslam_traverse) returned the true nearest map point for
+ *      78 of 697 and 82 of 810 in-range beams at the true pose; the median match was 0.37 m and 0.24 m away, the true nearest point 6 mm;
+ *   2. rejected beams poison the fit: beams outside the +-20 m reject stay in as (0, 0, 0) targets and are matched (H2) -- iterating the
+ *      step from 0.10 m / 0.03 rad off walks the pose 17 m away within 30 iterations;
+ *   3. the pose update is wrong under rotation: it is start + (t.x, t.y, theta) while the fit rotates about the world origin; the robot
+ *      position should become R r + t, the step drops the lever arm (R - I) r.
+ * pfslam_nearest and pfslam_register work on the handle's device-resident map and scan.  Like every entry point but the step functions both
+ * first book the frames in flight; both honour pfslam_set_trig.  Neither writes state that any other entry point reads -- not the pose, not
+ * buffers 11 / 12, not the tree: their scratch is their own.  No option makes a frame call them.
+ *
+ * pfslam_nearest: the exact nearest map node of n query points (xyz_host: n * 3 floats; best_host: n ints; d2_host: n floats or NULL), the
+ * counterpart of pfslam_traverse.  In float, one rounding per operation, in this order, no contraction:
+ *     d2(q, node) = ((nx - qx) * (nx - qx) + (ny - qy) * (ny - qy)) + (nz - qz) * (nz - qz)
+ * The result is the node with the smallest d2, the lowest node index among equal ones; a query with a non-finite coordinate gets index -1
+ * (and d2 = +inf).  Exact for every tree the library can hold -- KDTree::Create / Balance, grown by InsertNode, non-planar --: a
+ * branch-and-bound descent that backtracks through the parent links, no stack, no depth limit.
+ *
+ * pfslam_register: up to max_iters ICP iterations on the device, no host round trip in between (one launch, one copy, one wait).
+ *   start     float[3], or NULL = the handle's pose, read on the device
+ *   pose_out  float[3]
+ *   info      float[8] = {status, iterations completed, pairs, mean squared residual, 0, 0, 0, 0}; pairs and residual are those of the last
+ *             completed iteration (0 when there is none), except that status 2 reports the pair count that was too small
+ *   trace     NULL or max_iters x 8 floats; row k = {x', y', theta', x' - x, y' - y, theta' - theta, pairs, e}, written for completed
+ *             iterations only
+ *   status    0 = max_iters done, 1 = converged (eps), 2 = too few pairs, 3 = the pose turned non-finite
+ * Refused (non-zero, pfslam_last_error names the cause, outputs untouched): no map; n_beams > 4096; an option out of range (max_iters outside
+ * 1 .. 64, match / select / update outside 0 .. 1, max_dist not finite, an eps negative or not finite).
+ * Iteration k runs from p = (x, y, theta), p_0 = start.  All arithmetic is float, one rounding per operation, in the order written; csum is
+ * the canonical sum of pfslam_estimate above (n_beams <= 4096: one tile); R, A and t are indexed as in pfslam_icp's dbg29:
+ *   1. targets          (wx, wy) = CleanLidarScan(i, scan[i], theta)          in_i = |wx| < 20 && |wy| < 20
+ *                       t_i = in_i ? (x + wx, y + wy, 0) : (0, 0, 0)
+ *   2. correspondences  c_i = (x, y, z) of the node `match` selects for t_i; d2_i as in pfslam_nearest (a t_i that is not finite has no
+ *                       nearest node under match 1: c_i and d2_i are NaN)
+ *   3. validity         select 0: v_i = 1.   select 1: v_i = in_i && (max_dist <= 0 || d2_i <= max_dist * max_dist)
+ *                       nv = sum v_i;  select 1 and nv < max(min_pairs, 1): status 2, the result is p, stop
+ *   4. fit              mu = csum(v_i ? component : 0) / (float)nv for the six components
+ *                       A[j * 3 + r] = csum(v_i ? (t_i[r] + (-mu_t[r])) * (c_i[j] + (-mu_c[j])) : 0)
+ *                       svd3, R = U V^T, t = mu_c - R mu_t, theta = asin(R[1]) exactly as in pfslam_icp (select 0: that step bit for bit)
+ *   5. residual         e = csum(v_i ? d2_i : 0) / (float)nv
+ *   6. update           update 0: x' = x + t[0], y' = y + t[1]
+ *                       update 1: x' = (R[0] * x + R[3] * y) + t[0], y' = (R[1] * x + R[4] * y) + t[1]
+ *                       both: theta' = theta + theta_fit
+ *   7. stopping         x', y' or theta' not finite: status 3, the result is p, stop (the iteration does not count)
+ *                       otherwise p <- p', the trace row is written; status 1 and stop when |x' - x| < eps_xy && |y' - y| < eps_xy &&
+ *                       |theta' - theta| < eps_theta (an eps of 0 never passes); status 0 after max_iters
+ * With the defaults (exact neighbours, a 0.5 m gate, rejected beams left out, the rigid update) the six cases of
+ * tests/test_register_spec.py end within one map cell and one beam step of the pose their scan was cast from. */
+typedef struct pfslam_register_opts {
+    int32_t max_iters;  /* 1 .. 64 */
+    int32_t match;      /* 0 = the reference's traversal (pfslam_traverse), 1 = exact nearest neighbour (pfslam_nearest) */
+    int32_t select;     /* 0 = every beam, rejected ones as zero targets (the reference, H2);
+                           1 = in-range beams whose correspondence passes the gate */
+    int32_t update;     /* 0 = the reference's increment, 1 = rigid */
+    float   max_dist;   /* select 1: accepted when d2 <= max_dist * max_dist (float product); <= 0: no gate */
+    float   eps_xy, eps_theta;  /* stop when |dx| < eps_xy && |dy| < eps_xy && |dtheta| < eps_theta; 0: never */
+    int32_t min_pairs;  /* select 1: fewer accepted pairs ends the run; values below 1 count as 1 */
+} pfslam_register_opts;
+/* {40, 1, 1, 1, 0.5f, 1e-4f, 1e-5f, 3} */
+void pfslam_register_default_opts(pfslam_register_opts *opts);
+int pfslam_nearest(pfslam_handle *h, const float *xyz_host, int n, int32_t *best_host, float *d2_host);
+int pfslam_register(pfslam_handle *h, const float start[3], const pfslam_register_opts *opts, float pose_out[3], float info[8], float *trace);
 /* ---- round-5 frame loop: test and measurement support (no reference counterpart) ----
  * pfslam_set_serial(h, 1): every launch of every frame on ONE stream, in the order the four chains of a frame are enqueued (what the
  * environment variable PFSLAM_SERIAL=1 sets at creation).  Results and the cell rows' bookkeeping are the same as with the chains on their
