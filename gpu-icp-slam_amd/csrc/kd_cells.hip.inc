@@ -606,7 +606,7 @@ __global__ __launch_bounds__(64) void k_cells_update(pf::KdView tree, CellGeom g
             if (cr >= 0) ndr = tree.hot[cr];
             const float nx = __uint_as_float(nd.x), ny = __uint_as_float(nd.y);
             const uint32_t axis = nd.z >> 30;
-            if (!(fabsf(nx) < 1e6f && fabsf(ny) < 1e6f)) { give_up = true; break; } // a non-finite node (inserted under a NaN pose): no rows
+            if (!(fabsf(nx) < 1e6f && fabsf(ny) < 1e6f)) { give_up = true; break; } // a non-finite node (uploaded, or inserted under an infinite pose; a NaN pose inserts none): no rows
             float lb, ub;
             bounds(cxlo, cxhi, cylo, cyhi, nx, ny, lb, ub);
             U = fminf(U, ub);

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void k_reduce_groups(const short *__restrict__
     }
     const int slot = g * 64 + lane;
     if (g < groups && slot < n && (SPLIT == 1 || wave == 0)) {
-        const float a = (float)v; // |sum| <= 1081 x 8192 < 2^24
+        const float a = (float)v; // |sum| <= n_beams x largest |weight| <= 2^24 (upload_tree)
         const int i = order ? order[slot] : slot;
         fit[i] = a;
         const long long k1 = ((long long)f32_to_ordered(a) << 32) | (long long)(0xFFFFFFFFu - (uint32_t)(goff + i)); // (the GLOBAL index: a shard's keys merge with the other ranks')

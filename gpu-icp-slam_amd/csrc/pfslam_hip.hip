@@ -30,6 +30,7 @@
 #define PF_OCCUPIED_WEIGHT 4
 #define PF_EFFECTIVE_PARTICLES .7
 #define PF_CLAMP_VAL 113.0f /* (1 << 7) - 15, kernel.cu:518,1355 */
+#define PF_SUM_EXACT 16777216.0f /* 2^24: integers up to here are floats, so a sum of integers that stays below it is exact in any order */
 #define PF_SVD_EPSILON 0.00001f
 #define PF_SUM_TILE 4096
 #define PF_SCAN_TILE 1024
@@ -120,7 +121,7 @@ struct pfslam_handle {
     int *parent = nullptr;
     float *kz = nullptr, *kw = nullptr;
     std::vector<pfslam_node> h_nodes; // host mirror (topology + positions; w refreshed on demand)
-    bool integral_w = true; // every map weight is an integer (true for every map the SLAM step itself produces)
+    bool integral_w = true; // every map weight is an integer and n_beams x the largest magnitude <= 2^24 (true for every map the SLAM step itself produces)
     float w_absmax = 113.0f; // largest |weight| the map can hold: of the uploaded map, or the clamp of the map update (113) if that is larger
     // scoring
     float *fit = nullptr, *partial = nullptr;
@@ -1230,7 +1231,7 @@ static int upload_tree(pfslam_handle *h, const pfslam_node *nodes, int n, std::v
     }
     // pass 1 (parallel): links in range, planar, integer weights, on the lattice of the config -- x == fl(k * res) bit for bit, the way
     // cell_to_point (ROUND_FRAC, kernel.cu:52) makes map points
-    std::atomic<int> bad{-1}, nonplanar{0}, nonintegral{0}, offlattice{0}, wmax_bits{0};
+    std::atomic<int> bad{-1}, badw{-1}, nonplanar{0}, nonintegral{0}, offlattice{0}, wmax_bits{0};
     const float rx = h->cfg.map_res_x, ry = h->cfg.map_res_y, ix = 1.0f / rx, iy = 1.0f / ry;
     const float xmax = rx * (float)PF_LATTICE_KMAX, ymax = ry * (float)PF_LATTICE_KMAX;
     parallel_chunks(n, [&](int lo, int hi, int) {
@@ -1247,9 +1248,15 @@ static int upload_tree(pfslam_handle *h, const pfslam_node *nodes, int n, std::v
             z[i] = nd.z;
             w[i] = nd.w;
             np |= nd.z != 0.0f;
-            // |w| <= 2^13 keeps every partial sum of 1081 weights below 2^24, i.e. exact in any order
-            ni |= !(nd.w == (float)(int)nd.w && fabsf(nd.w) <= 8192.0f);
-            wm = nd.w == nd.w ? std::max(wm, fabsf(nd.w)) : INFINITY;
+            if (!(fabsf(nd.w) < INFINITY)) { // NaN too: the reference's measurement update has no defined result for such a fit (include/pfslam.h)
+                int none = -1;
+                badw.compare_exchange_strong(none, i);
+                return;
+            }
+            // integers, and (below, once the largest magnitude is known) n_beams x |w| <= 2^24: every partial sum of a particle's beams is
+            // then an integer a float holds, i.e. exact in any order
+            ni |= !(fabsf(nd.w) <= PF_SUM_EXACT && nd.w == (float)(int)nd.w);
+            wm = std::max(wm, fabsf(nd.w));
             if (!ol) {
                 if (!(fabsf(nd.x) < xmax && fabsf(nd.y) < ymax)) ol = true; // |k| < 2^20 cells per axis (PF_LATTICE_KMAX); NaN fails
                 else {
@@ -1269,8 +1276,16 @@ static int upload_tree(pfslam_handle *h, const pfslam_node *nodes, int n, std::v
         if (ol) offlattice = 1;
     });
     if (bad.load() >= 0) return fail("pfslam_set_map: node " + std::to_string(bad.load()) + " has out-of-range links or axis");
+    if (badw.load() >= 0) return fail("pfslam_set_map: node " + std::to_string(badw.load()) + " has a weight that is not finite");
+    float wabs;
+    {
+        const int wb = wmax_bits.load();
+        memcpy(&wabs, &wb, 4);
+        wabs = std::max(wabs, PF_CLAMP_VAL); // the map update moves a weight by -1 / +4 and clamps to +-113: never beyond the larger of the two
+    }
     const int planar = nonplanar.load() ? 0 : 1;
-    const bool integral = nonintegral.load() == 0, lattice = planar && offlattice.load() == 0;
+    const bool integers = nonintegral.load() == 0, lattice = planar && offlattice.load() == 0;
+    const bool integral = integers && (double)wabs * (double)h->nb <= (double)PF_SUM_EXACT; // (pfslam_create: at most 4096 beams; 4096 x 4096 = 2^24)
     parallel_chunks(n, [&](int lo, int hi, int) { // pass 2: the hot records need `planar`
         for (int i = lo; i < hi; i++) {
             const pfslam_node &nd = nodes[i];
@@ -1282,14 +1297,9 @@ static int upload_tree(pfslam_handle *h, const pfslam_node *nodes, int n, std::v
     HIPCHK(hipMemcpyAsync(h->parent, par, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->kz, z, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->kw, w, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    float wabs;
-    {
-        const int wb = wmax_bits.load();
-        memcpy(&wabs, &wb, 4);
-        wabs = std::max(wabs, PF_CLAMP_VAL); // the map update moves a weight by -1 / +4 and clamps to +-113: never beyond the larger of the two
-    }
     // [1 .. 3]: for the ranks that adopt this tree (pfslam_shard_balance_adopt); [2]: 0 = weights not all integers, else their largest magnitude
-    const int state[4] = {n, planar, integral ? (int)std::min(wabs, 1e9f) : 0, lattice ? 1 : 0};
+    // (an adopting rank applies its own beam count to it)
+    const int state[4] = {n, planar, integers ? (int)std::min(wabs, 1e9f) : 0, lattice ? 1 : 0};
     HIPCHK(hipMemcpyAsync(h->kd_state, state, 16, hipMemcpyHostToDevice, h->stream));
     if (own && own->data() == nodes && (int)own->size() == n) h->h_nodes.swap(*own); // (while the copies are in flight)
     else h->h_nodes.assign(nodes, nodes + n);
@@ -1556,8 +1566,9 @@ static int score_chunks(const pfslam_handle *h)
     int chunks = (target + groups - 1) / groups;
     chunks = std::max(1, std::min(chunks, h->nb)); // small particle counts go down to one beam per wave
     // Beam-chunk partials added afterwards equal the reference's sequential beam-order float sum only when every term is an
-    // integer (any map the SLAM step builds: 0 / -100 initial, -1 / +4 steps, clamp +-113).  A map uploaded through
-    // pfslam_set_map with other weights is scored in one chunk: slower, but kernEvaluateParticlesKD's own summation order.
+    // integer and no partial sum can pass 2^24 (any map the SLAM step builds: 0 / -100 initial, -1 / +4 steps, clamp +-113; upload_tree
+    // holds an uploaded map to n_beams x largest |weight| <= 2^24).  A map uploaded through pfslam_set_map with other weights is scored
+    // in one chunk: slower, but kernEvaluateParticlesKD's own summation order.
     if (!h->integral_w) chunks = 1;
     return chunks;
 }

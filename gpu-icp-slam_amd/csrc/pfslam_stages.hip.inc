@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void k_reduce_partials_minmax(const float *__r
                 for (int k = 0; k < 32; k++) ia += v[k];
             }
             for (; c < chunks; c++) ia += p[(size_t)c * n + slot];
-            a = (float)ia; // |sum| <= 1081 x 8192 < 2^24
+            a = (float)ia; // |sum| <= n_beams x largest |weight| <= 2^24 (upload_tree)
         }
         for (; c + 64 <= chunks; c += 64) {
             float v[64];
@@ -2861,7 +2861,7 @@ extern "C" int pfslam_shard_balance_adopt(pfslam_handle *h)
     HIPCHK(hipStreamSynchronize(h->stream));
     if (st[0] != h->kd_size) return fail("pfslam_shard_balance_adopt: the broadcast map has " + std::to_string(st[0]) + " nodes, this rank's " + std::to_string(h->kd_size));
     h->planar = st[1];
-    h->integral_w = st[2] != 0;
+    h->integral_w = st[2] != 0 && (double)st[2] * (double)h->nb <= (double)PF_SUM_EXACT; // (upload_tree's class, with this rank's beam count)
     h->w_absmax = st[2] != 0 ? (float)st[2] : 113.0f;
     h->lattice_ok = st[3] != 0;
     h->mirror_n = 0; // the host mirror knows nothing of the new topology: read back whole when somebody asks (pfslam_get_map)

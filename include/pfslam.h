@@ -129,6 +129,20 @@ int pfslam_get_trace(pfslam_handle *h, int32_t out[8]);
 int pfslam_get_cells(pfslam_handle *h, int which, int32_t *out, int cap, int *n);
 
 /* ---- state upload ---- */
+/* pfslam_set_map: a tree as KDTree::Create / InsertNode leave it.  Refused (non-zero, pfslam_last_error names the node, the loaded map
+ * stays): a link or axis out of range, n above kd_capacity, and a weight that is NaN or infinite -- kernUpdateWeights converts the smallest
+ * fit to int (kernel.cu:297-304), which has no defined result for such a sum, and thrust::minmax_element never selects a NaN.  Every finite
+ * weight is accepted and scored; pfslam_measurement_update and the frames behind it are defined only while the smallest fit fits an int,
+ * i.e. while n_beams x the largest |weight| < 2^31 -- beyond that the reference's conversion has no defined result either.  Integer weights with n_beams x the largest |weight| <= 2^24 (every map the SLAM step builds: +-113) are summed in
+ * beam chunks, exact in any order; any other map is summed beam by beam in the reference's order, in one chunk per particle -- the same
+ * bits as kernEvaluateParticlesKD either way, the second slower.  Coordinates may be anything: a node that is off the lattice of the
+ * configured resolution, beyond 2^20 cells from the origin, NaN or infinite only turns the lattice-cell rows off for the whole map (the
+ * distance to a NaN node is NaN and never the smallest, as in the reference).  KDTree::Create and Balance (pfslam_kd_create, the
+ * re-balance of frame % balance_period == 5) sort the coordinates and are not defined on NaN.
+ * pfslam_set_particles: n = cfg.n_particles poses and weights, any float.  A NaN, infinite or huge pose scores what the reference's
+ * traversal gives it (a NaN or infinite query ends at the root) and costs the other particles nothing but the organisation of the pass:
+ * its wave takes the plain traversal, and a non-finite mean of the first 1024 particles leaves the window of the cell rows where it is.
+ * The 2-D map update converts the pose to int (kernel.cu:551-577): pfslam_step_grid is defined for finite poses only. */
 int pfslam_set_map(pfslam_handle *h, const pfslam_node *nodes, int n);
 int pfslam_set_particles(pfslam_handle *h, const pfslam_particle *p, int n);
 int pfslam_set_scan(pfslam_handle *h, const float *scan_host, int n_beams);
@@ -380,7 +394,8 @@ int pfslam_estimate(pfslam_handle *h, float out[16]);
  * counterpart of pfslam_traverse.  In float, one rounding per operation, in this order, no contraction:
  *     d2(q, node) = ((nx - qx) * (nx - qx) + (ny - qy) * (ny - qy)) + (nz - qz) * (nz - qz)
  * The result is the node with the smallest d2, the lowest node index among equal ones; a query with a non-finite coordinate gets index -1
- * (and d2 = +inf).  Exact for every tree the library can hold -- KDTree::Create / Balance, grown by InsertNode, non-planar --: a
+ * (and d2 = +inf).  A node with a NaN coordinate has d2 = NaN and is never the result.  Exact for every tree the library can hold --
+ * KDTree::Create / Balance, grown by InsertNode, non-planar --: a
  * branch-and-bound descent that backtracks through the parent links, no stack, no depth limit.
  *
  * pfslam_register: up to max_iters ICP iterations on the device, no host round trip in between (one launch, one copy, one wait).

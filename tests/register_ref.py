@@ -25,7 +25,8 @@ def csum(v):
 
 
 def nearest(tree, xyz, chunk=256):
-    """(index int32, d2 float32) of the exact nearest node of every query; -1 / +inf for a query with a non-finite coordinate."""
+    """(index int32, d2 float32) of the exact nearest node of every query; -1 / +inf for a query with a non-finite coordinate.  A node whose
+    d2 is NaN (a node with a NaN coordinate) is never the nearest: `d2 < best` is false for it."""
     q = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
     nx, ny, nz = [np.ascontiguousarray(tree[k], np.float32)[None, :] for k in ("x", "y", "z")]
     best = np.empty(len(q), np.int32)
@@ -35,6 +36,7 @@ def nearest(tree, xyz, chunk=256):
             c = q[lo:lo + chunk]
             dx, dy, dz = nx - c[:, 0:1], ny - c[:, 1:2], nz - c[:, 2:3]
             d = (dx * dx + dy * dy) + dz * dz
+            d = np.where(np.isnan(d), np.float32(np.inf), d)      # (numpy's argmin would take a NaN for the minimum)
             b = d.argmin(axis=1)
             best[lo:lo + chunk] = b
             d2[lo:lo + chunk] = d[np.arange(len(c)), b]
