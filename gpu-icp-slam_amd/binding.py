@@ -26,7 +26,7 @@ SYMBOLS = [
     "pfslam_kd_create", "pfslam_kd_insert_list", "pfslam_kd_insert_node", "pfslam_kd_balance", "pfslam_set_timing", "pfslam_get_timers", "pfslam_resample_plan", "pfslam_resample_gather", "pfslam_maybe_balance", "pfslam_kd_size", "pfslam_topology_update", "pfslam_find_walls",
     "pfslam_check_loop_closure", "pfslam_get_topology", "pfslam_set_topology", "pfslam_get_closures", "pfslam_score_census", "pfslam_set_census", "pfslam_get_census_log", "pfslam_ubench_gather", "pfslam_plan_stats", "pfslam_cell_stats", "pfslam_kd_parallel_sort", "pfslam_kd_sort_threads", "pfslam_kd_whole_node",
     "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_estimate", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
-    "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts",
+    "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
 
@@ -155,6 +155,7 @@ def load():
     L.pfslam_register_default_opts.argtypes = [vp]
     L.pfslam_nearest.argtypes = [vp, vp, i32, vp, vp]
     L.pfslam_register.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.pfslam_register_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.pfslam_debug_check_cells.argtypes = [vp, vp]
     L.pfslam_set_probe.argtypes = [vp, i32]
     L.pfslam_get_probe.argtypes = [vp, vp, i32, vp, vp]
@@ -578,6 +579,25 @@ class PfSlam:
         it = int(info[1])
         return {"pose": pose, "status": int(info[0]), "iterations": it, "pairs": int(info[2]), "residual": float(info[3]),
                 "trace": trace[:it].copy()}
+
+    def register_batch(self, starts, **opts):
+        """pfslam_register from every row of `starts` (m x 3) in one launch (include/pfslam.h, pfslam_register_batch); options as for
+        register().  Returns poses (m, 3), status, iterations, pairs (int arrays), residual (float32 array), info (m, 8: the rows as
+        pfslam_register returns them) and best, the row the header's rule picks (-1: none is eligible).  Row r is bit for bit
+        register(starts[r], **opts) without its trace."""
+        o = RegisterOpts()
+        self.L.pfslam_register_default_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in dict(RegisterOpts._fields_):
+                raise TypeError("register_batch() has no option %r" % k)
+            setattr(o, k, v)
+        st = np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, 3)
+        m = len(st)
+        poses, info = np.zeros((max(m, 1), 3), np.float32), np.zeros((max(m, 1), 8), np.float32)
+        best = C.c_int(-1)
+        _chk(self.L.pfslam_register_batch(self._h, _p(st), m, C.byref(o), _p(poses), _p(info), C.byref(best)), "pfslam_register_batch")
+        return {"poses": poses, "status": info[:, 0].astype(np.int32), "iterations": info[:, 1].astype(np.int32),
+                "pairs": info[:, 2].astype(np.int32), "residual": info[:, 3].copy(), "info": info, "best": int(best.value)}
 
     def frame_mode(self):
         out = (C.c_int * 4)()

@@ -276,6 +276,32 @@ bool pfslamRegister(glm::vec3 start, int max_iters, glm::vec3 &pose, int *status
     if (iterations) *iterations = (int)info[1];
     return true;
 }
+bool pfslamRegisterBatch(const glm::vec3 *starts, int m, int max_iters, glm::vec3 *poses, int *status, int *best)
+{
+    if (!g_handle || !starts || !poses) return false;
+    if (m < 1) {
+        fprintf(stderr, "pfslamRegisterBatch: m must be 1 .. 4096\n");
+        return false;
+    }
+    pfslam_register_opts o;
+    pfslam_register_default_opts(&o);
+    if (max_iters > 0) o.max_iters = max_iters;
+    std::vector<float> s((size_t)m * 3), p((size_t)m * 3), info((size_t)m * 8);
+    for (int r = 0; r < m; r++) {
+        s[3 * (size_t)r] = starts[r].x; s[3 * (size_t)r + 1] = starts[r].y; s[3 * (size_t)r + 2] = starts[r].z;
+    }
+    int b = -1;
+    if (pfslam_register_batch(g_handle, s.data(), m, &o, p.data(), info.data(), &b)) { // (an empty map is a state of the filter, not a failure of the program)
+        fprintf(stderr, "pfslamRegisterBatch: %s\n", pfslam_last_error());
+        return false;
+    }
+    for (int r = 0; r < m; r++) {
+        poses[r] = glm::vec3(p[3 * (size_t)r], p[3 * (size_t)r + 1], p[3 * (size_t)r + 2]);
+        if (status) status[r] = (int)info[8 * (size_t)r];
+    }
+    if (best) *best = b;
+    return true;
+}
 std::vector<std::pair<int, int>> pfslamLoopClosures()
 {
     std::vector<std::pair<int, int>> out;

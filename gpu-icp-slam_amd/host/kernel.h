@@ -68,6 +68,11 @@ bool pfslamPoseEstimate(glm::vec3 &mean, float cov[9], float *neff);
 // first waits for the frames in flight.  status: 0 max_iters done, 1 converged, 2 too few pairs, 3 not finite; iterations may be null.
 // false (and a line on stderr): no live filter, no map yet, or an option out of range; the outputs are then untouched.
 bool pfslamRegister(glm::vec3 start, int max_iters, glm::vec3 &pose, int *status, int *iterations);
+// pfslamRegister from m start poses in one launch (include/pfslam.h, pfslam_register_batch): poses[r] and status[r] are what pfslamRegister
+// gives from starts[r]; *best is the row the library's rule picks -- the smallest residual among the runs that kept at least half as many
+// pairs as the run that kept most -- or -1 when no run completed an iteration.  status and best may be null.  false (and a line on
+// stderr): no live filter, no map yet, m outside 1 .. 4096 or an option out of range; the outputs are then untouched.
+bool pfslamRegisterBatch(const glm::vec3 *starts, int m, int max_iters, glm::vec3 *poses, int *status, int *best);
 // Map export for an end-to-end comparison: the point-cloud map as the reference's viewer filters it
 // (nodes with w > -100, main.cpp:269-284) -> PREFIX.kd.bin (float x, y, z, w per point, in node order) + PREFIX.kd.csv, and
 // the 2-D occupancy grid -> PREFIX.grid.i8 (dim.x * dim.y signed bytes, cell (x, y) at x * dim.x + y) + PREFIX.grid.pgm

@@ -1,5 +1,5 @@
 // replay_main.cpp -- headless counterpart of the reference's main loop (main.cpp:47-96, 175-229):
-//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [export=PREFIX]
+//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [export=PREFIX]
 //     grid           the 2-D occupancy-grid stages instead of the point-cloud ones
 //     loop           UpdateTopology + CheckLoopClosure at the end of every frame (kernel.cu:1750-1751, commented out in
 //                    the reference's shipped step); loop-closure proposals are printed per frame
@@ -8,6 +8,9 @@
 //                    (pfslamPoseEstimate), as decimals and as float bits
 //     register=K     a further line per frame: the pose pfslamRegister reaches from the frame's pose in at most K iterations (the frame's scan
 //                    against the frame's map; the filter is not changed), its status and iteration count, as decimals and as float bits
+//     multistart=K   a further line per frame: pfslamRegisterBatch from the nine starts frame's pose + (dx, dy, 0), dx, dy in {-0.1, 0, 0.1} m
+//                    (row = 3 * index of dx + index of dy), at most K iterations each: the row it picks and that row's pose, as decimals
+//                    and as float bits ("best -1" and no pose when no run completed an iteration)
 //     export=PREFIX  after the last frame: the map as the reference's viewer filters it (KD nodes with w > -100,
 //                    main.cpp:269-284) and the occupancy grid -> PREFIX.kd.bin / .kd.csv / .grid.i8 / .grid.pgm
 // iteration 0: Free + Init; then particleFilter(pbo=NULL, ++iteration, lidar) until the scans run out.
@@ -22,14 +25,14 @@
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [export=PREFIX]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [export=PREFIX]\n", argv[0]);
         return 1;
     }
     Scene *scene = new Scene(argv[1]);
     Lidar *lidar = new Lidar(argv[2]);
     size_t last = lidar->scans.size() - 1;
     bool loop = false, estimate = false;
-    int register_iters = 0;
+    int register_iters = 0, multistart_iters = 0;
     std::string export_prefix;
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "grid") == 0) pfslamUseGridMap(true);
@@ -37,6 +40,7 @@ int main(int argc, char **argv)
         else if (strncmp(argv[i], "resampler=", 10) == 0) pfslamSetResampler(atoi(argv[i] + 10));
         else if (strncmp(argv[i], "estimate=", 9) == 0) estimate = atoi(argv[i] + 9) != 0;
         else if (strncmp(argv[i], "register=", 9) == 0) register_iters = atoi(argv[i] + 9);
+        else if (strncmp(argv[i], "multistart=", 11) == 0) multistart_iters = atoi(argv[i] + 11);
         else if (strncmp(argv[i], "export=", 7) == 0) export_prefix = argv[i] + 7;
         else if (atoi(argv[i]) > 0) last = std::min(last, (size_t)atoi(argv[i]));
     }
@@ -88,6 +92,23 @@ int main(int argc, char **argv)
                 printf("register %zu pose %.6f %.6f %.6f status %d iterations %d bits %08x %08x %08x\n", iteration, r.x, r.y, r.z, status, iters, b[0], b[1], b[2]);
             } else {
                 printf("register %zu none\n", iteration);
+            }
+        }
+        if (multistart_iters > 0) {
+            const float off[3] = {-0.1f, 0.0f, 0.1f};
+            glm::vec3 starts[9], poses[9];
+            for (int a = 0; a < 3; a++)
+                for (int b = 0; b < 3; b++) starts[3 * a + b] = glm::vec3(pos.x + off[a], pos.y + off[b], pos.z);
+            int best = -1;
+            if (!pfslamRegisterBatch(starts, 9, multistart_iters, poses, nullptr, &best)) {
+                printf("multistart %zu none\n", iteration);
+            } else if (best < 0) {
+                printf("multistart %zu best -1\n", iteration);
+            } else {
+                const glm::vec3 r = poses[best];
+                unsigned int b[3];
+                memcpy(&b[0], &r.x, 4); memcpy(&b[1], &r.y, 4); memcpy(&b[2], &r.z, 4);
+                printf("multistart %zu best %d pose %.6f %.6f %.6f bits %08x %08x %08x\n", iteration, best, r.x, r.y, r.z, b[0], b[1], b[2]);
             }
         }
     }

@@ -169,6 +169,11 @@ class ShardedSlam:
         is -- no collective -- and returns the unsharded handle's bits on every rank."""
         return self.eng.register(start, **opts)
 
+    def register_batch(self, starts, **opts):
+        """pfslam_register from many start poses in one launch (pfslam_register_batch): passed through like register -- replicated map
+        and scan, no collective, the unsharded handle's bits on every rank."""
+        return self.eng.register_batch(starts, **opts)
+
     def _all_gather(self, dst, src, which):
         """Collective `which` (0 pose blocks, 1 keys, 2 weights) of the frame being enqueued, in the stream the engine names for it
         (GPU engines: pfslam_shard_stream -- stream order is all the ordering there is; gloo completes it before it returns)."""

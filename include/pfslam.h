@@ -28,6 +28,7 @@
  *   pfslam_traverse                    findCorrespondenceIndexKD          kernel.cu:924-972
  *   pfslam_nearest / pfslam_register   no counterpart: the exact nearest map node, and transformPointICP iterated on the device with
  *                                      its three defects optional (see pfslam_register below)
+ *   pfslam_register_batch              no counterpart: pfslam_register from many start poses in one launch, and the pick of the best run
  *   pfslam_topology_update, find_walls,
  *   check_loop_closure, get_topology   UpdateTopology / FindWalls / CheckLoopClosure   kernel.cu:623-795
  *   pfslam_shard_disperse / score / weights / finish   particleFilter split where a multi-GPU caller places its three
@@ -442,6 +443,36 @@ typedef struct pfslam_register_opts {
 void pfslam_register_default_opts(pfslam_register_opts *opts);
 int pfslam_nearest(pfslam_handle *h, const float *xyz_host, int n, int32_t *best_host, float *d2_host);
 int pfslam_register(pfslam_handle *h, const float start[3], const pfslam_register_opts *opts, float pose_out[3], float info[8], float *trace);
+/* pfslam_register_batch: m independent registrations of the handle's scan against the handle's map from m start poses -- one launch, one
+ * copy back, one wait; one workgroup per run, so up to a whole device's compute units work where pfslam_register uses one.
+ *   starts     m x 3 floats (none may be left out: there is no "handle's pose" row)
+ *   poses_out  m x 3 floats
+ *   info       m x 8 floats, row r as pfslam_register's info
+ *   best       NULL or one int
+ * Rows.  Row r of poses_out and info is bit for bit what pfslam_register(h, starts + 3 r, opts, ...) returns: that call is the definition,
+ * for a start that is not finite and for rows that end with status 2 or 3 as well.  Runs do not wait for one another: one that stops early
+ * makes room for the next.  There is no per-iteration trace; pfslam_register from the same start is the same run and has one.
+ * *best is decided from info alone, on the host:
+ *   eligible    rows with status 0 or 1, at least one completed iteration and a finite residual
+ *   P           the largest pair count among the eligible rows
+ *   candidates  the eligible rows with 2 * pairs >= P
+ *   best        the candidate with the smallest residual; among equal residuals the one with more pairs, then the lowest row;
+ *               -1 when no row is eligible
+ *   Why both: a run that keeps a handful of pairs can have any residual (42 beams that happen to lie on a wall fit it perfectly), so the
+ *   residual alone is no measure; the pair count alone picks wrong too -- from a 3 x 3 x 3 grid of starts (+-0.4 m, +-0.15 rad) around
+ *   (0.5, 0.3, 0.1) on the 4000-point map of tests/test_register_spec.py it chose a run with 802 pairs that ended 48 mm off over one with
+ *   801 pairs that ended 0.5 mm off.  Many starts are needed at all because from (10, -8, 0.3) only 6 of the 27 runs of that grid end
+ *   within one map cell and one beam step (tests/test_register_batch_spec.py).
+ * Refused (non-zero, pfslam_last_error names the cause, outputs untouched): a NULL argument other than best; m outside 1 .. 4096; no map;
+ * n_beams > 4096; every option pfslam_register refuses.
+ *   The cap of 4096 bounds one launch.  Measured on one MI355X: 4096 rows of 40 iterations each, none stopping early, 1081 beams, take
+ *   0.41 s on a 100 000-point map and 0.16 s on a 4000-point map (profiles/register_batch.txt; the estimate had been about a second).
+ * Like pfslam_register it first books the frames in flight and then runs on the handle's stream, honours pfslam_set_trig, reads the handle's
+ * device-resident map and scan and writes no state another entry point reads: its start and result buffers are its own (they belong to
+ * the handle, grow when a call needs more and go with pfslam_destroy), the per-run scratch is on chip.  The map and the scan of a sharded
+ * handle are replicated, so every rank gets the unsharded handle's bits. */
+int pfslam_register_batch(pfslam_handle *h, const float *starts /* m x 3 */, int m, const pfslam_register_opts *opts,
+                          float *poses_out /* m x 3 */, float *info /* m x 8 */, int *best /* may be NULL */);
 /* ---- round-5 frame loop: test and measurement support (no reference counterpart) ----
  * pfslam_set_serial(h, 1): every launch of every frame on ONE stream, in the order the four chains of a frame are enqueued (what the
  * environment variable PFSLAM_SERIAL=1 sets at creation).  Results and the cell rows' bookkeeping are the same as with the chains on their
