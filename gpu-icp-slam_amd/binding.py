@@ -26,7 +26,7 @@ SYMBOLS = [
     "pfslam_kd_create", "pfslam_kd_insert_list", "pfslam_kd_insert_node", "pfslam_kd_balance", "pfslam_set_timing", "pfslam_get_timers", "pfslam_resample_plan", "pfslam_resample_gather", "pfslam_maybe_balance", "pfslam_kd_size", "pfslam_topology_update", "pfslam_find_walls",
     "pfslam_check_loop_closure", "pfslam_get_topology", "pfslam_set_topology", "pfslam_get_closures", "pfslam_score_census", "pfslam_set_census", "pfslam_get_census_log", "pfslam_ubench_gather", "pfslam_plan_stats", "pfslam_cell_stats", "pfslam_kd_parallel_sort", "pfslam_kd_sort_threads", "pfslam_kd_whole_node",
     "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_estimate", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
-    "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch",
+    "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch", "pfslam_search", "pfslam_search_default_opts",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
 
@@ -45,6 +45,12 @@ class RegisterOpts(C.Structure):
     """pfslam_register_opts (include/pfslam.h)."""
     _fields_ = [("max_iters", C.c_int32), ("match", C.c_int32), ("select", C.c_int32), ("update", C.c_int32),
                 ("max_dist", C.c_float), ("eps_xy", C.c_float), ("eps_theta", C.c_float), ("min_pairs", C.c_int32)]
+
+
+class SearchOpts(C.Structure):
+    """pfslam_search_opts (include/pfslam.h)."""
+    _fields_ = [("half_x", C.c_int32), ("half_y", C.c_int32), ("half_theta", C.c_int32), ("stride", C.c_int32),
+                ("step_theta", C.c_float), ("max_dist", C.c_float), ("reserved_", C.c_int32 * 2)]
 
 
 REGISTER_STATUS = {0: "max_iters", 1: "converged", 2: "too_few_pairs", 3: "not_finite"}
@@ -156,6 +162,9 @@ def load():
     L.pfslam_nearest.argtypes = [vp, vp, i32, vp, vp]
     L.pfslam_register.argtypes = [vp, vp, vp, vp, vp, vp]
     L.pfslam_register_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.pfslam_search_default_opts.restype = None
+    L.pfslam_search_default_opts.argtypes = [vp]
+    L.pfslam_search.argtypes = [vp, vp, vp, vp, vp, vp]
     L.pfslam_debug_check_cells.argtypes = [vp, vp]
     L.pfslam_set_probe.argtypes = [vp, i32]
     L.pfslam_get_probe.argtypes = [vp, vp, i32, vp, vp]
@@ -598,6 +607,34 @@ class PfSlam:
         _chk(self.L.pfslam_register_batch(self._h, _p(st), m, C.byref(o), _p(poses), _p(info), C.byref(best)), "pfslam_register_batch")
         return {"poses": poses, "status": info[:, 0].astype(np.int32), "iterations": info[:, 1].astype(np.int32),
                 "pairs": info[:, 2].astype(np.int32), "residual": info[:, 3].copy(), "info": info, "best": int(best.value)}
+
+    def search(self, centre=None, scores=False, **opts):
+        """Windowed correlative scan-to-map search (include/pfslam.h, pfslam_search) around `centre` (None: the handle's pose).  Options by
+        name (half_x, half_y, half_theta, stride, step_theta, max_dist) over pfslam_search_default_opts.  Returns pose, status (0 ok,
+        2 no heading has an in-range beam), index (the winner's k, -1 with status 2), beams, mean_d2, score, candidates, qcap, info (the
+        eight floats) and, with scores=True, scores: S of every candidate, shaped (2 half_theta + 1, 2 half_y + 1, 2 half_x + 1).  Reads
+        the handle's state, writes none of it."""
+        o = SearchOpts()
+        self.L.pfslam_search_default_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("half_x", "half_y", "half_theta", "stride", "step_theta", "max_dist"):
+                raise TypeError("search() has no option %r" % k)
+            setattr(o, k, v)
+        pose, info = np.zeros(3, np.float32), np.zeros(8, np.float32)
+        c = None if centre is None else np.ascontiguousarray(centre, dtype=np.float32).reshape(-1)
+        if c is not None and c.shape != (3,):
+            raise ValueError("search(): centre must be (x, y, theta), got %d values" % c.size)
+        vol = None
+        if scores:
+            shape = tuple(2 * max(int(v), 0) + 1 for v in (o.half_theta, o.half_y, o.half_x))
+            if shape[0] * shape[1] * shape[2] <= 1 << 24:     # (a larger window is the library's to refuse)
+                vol = np.zeros(shape, np.int32)
+        _chk(self.L.pfslam_search(self._h, None if c is None else _p(c), C.byref(o), _p(pose), _p(info), None if vol is None else _p(vol)), "pfslam_search")
+        out = {"pose": pose, "status": int(info[0]), "index": int(info[1]), "beams": int(info[2]), "mean_d2": float(info[3]), "score": int(info[4]),
+               "candidates": int(info[5]), "qcap": int(info[6]), "info": info}
+        if scores:
+            out["scores"] = vol
+        return out
 
     def frame_mode(self):
         out = (C.c_int * 4)()

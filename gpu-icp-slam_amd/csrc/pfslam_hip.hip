@@ -153,6 +153,13 @@ struct pfslam_handle {
     float *reg_tar = nullptr, *reg_cor = nullptr, *reg_out = nullptr; // pfslam_register's own scratch (allocated on first use): targets, correspondences, pose + info + trace
     float *regb_in = nullptr, *regb_out = nullptr; // pfslam_register_batch's own buffers: m x 3 starts, m x 12 result rows; they grow with m
     int regb_cap = 0, regb_cus = 0;                // rows they hold; compute units of the device (read on first use)
+    // pfslam_search's own buffers; each grows when a call needs more: the distance field, the end-point cells per (heading, beam), the
+    // in-range count per heading, the score volume (only when a caller asks for it), and key + box + result row
+    uint16_t *srch_field = nullptr;
+    int2 *srch_ends = nullptr;
+    int *srch_nin = nullptr, *srch_scores = nullptr;
+    unsigned long long *srch_state = nullptr;
+    size_t srch_field_cap = 0, srch_ends_cap = 0, srch_nin_cap = 0, srch_scores_cap = 0;
     float *est_part = nullptr; // pfslam_estimate: 11 tile sums per 4096-particle tile of the GLOBAL cloud, then the 16 output floats
     // grid path
     int8_t *grid = nullptr;
@@ -1033,7 +1040,7 @@ extern "C" int pfslam_destroy(pfslam_handle *h)
                     h->fit, h->fit_i, h->partial, h->mkey, h->order2, h->cells, h->stats, h->pose, h->start, h->icp_tar, h->icp_cor, h->icp_dbg,
                     h->free_mask, h->blk_cnt, h->wall_cell, h->free_cell, h->wall_pts, h->free_pts,
                     h->wall_c, h->free_c, h->counts, h->tile_r, h->tile_r2, h->sums, h->cdf,
-                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
+                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->srch_field, h->srch_ends, h->srch_nin, h->srch_scores, h->srch_state, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (h->own_global) {
@@ -2441,3 +2448,4 @@ static int frame_v2_finish(pfslam_handle *h);
 #include "pfslam_frame.hip.inc"
 #include "pfslam_register.hip.inc"
 #include "pfslam_register_batch.hip.inc"
+#include "pfslam_search.hip.inc"

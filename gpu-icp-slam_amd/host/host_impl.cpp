@@ -302,6 +302,21 @@ bool pfslamRegisterBatch(const glm::vec3 *starts, int m, int max_iters, glm::vec
     if (best) *best = b;
     return true;
 }
+bool pfslamSearch(glm::vec3 centre, glm::vec3 &pose, int *index)
+{
+    if (!g_handle) return false;
+    pfslam_search_opts o;
+    pfslam_search_default_opts(&o);
+    const float c[3] = {centre.x, centre.y, centre.z};
+    float p[3], info[8];
+    if (pfslam_search(g_handle, c, &o, p, info, nullptr)) { // (an empty map is a state of the filter, not a failure of the program)
+        fprintf(stderr, "pfslamSearch: %s\n", pfslam_last_error());
+        return false;
+    }
+    pose = glm::vec3(p[0], p[1], p[2]);
+    if (index) *index = (int)info[1];
+    return true;
+}
 std::vector<std::pair<int, int>> pfslamLoopClosures()
 {
     std::vector<std::pair<int, int>> out;

@@ -73,6 +73,12 @@ bool pfslamRegister(glm::vec3 start, int max_iters, glm::vec3 &pose, int *status
 // pairs as the run that kept most -- or -1 when no run completed an iteration.  status and best may be null.  false (and a line on
 // stderr): no live filter, no map yet, m outside 1 .. 4096 or an option out of range; the outputs are then untouched.
 bool pfslamRegisterBatch(const glm::vec3 *starts, int m, int max_iters, glm::vec3 *poses, int *status, int *best);
+// Windowed correlative search of the live filter's scan against its map (no reference counterpart; include/pfslam.h, pfslam_search): every
+// pose of the default window (pfslam_search_default_opts: +-20 cells, +-16 heading steps of 0.0125 rad) around `centre` scored against a
+// distance field of the map; pose is the best candidate, *index its number (-1: no heading has an in-range beam, pose is the centre).
+// Reads the filter, changes nothing in it; like getPCData it first waits for the frames in flight.  index may be null.  false (and a
+// line on stderr): no live filter or no map yet; the outputs are then untouched.
+bool pfslamSearch(glm::vec3 centre, glm::vec3 &pose, int *index);
 // Map export for an end-to-end comparison: the point-cloud map as the reference's viewer filters it
 // (nodes with w > -100, main.cpp:269-284) -> PREFIX.kd.bin (float x, y, z, w per point, in node order) + PREFIX.kd.csv, and
 // the 2-D occupancy grid -> PREFIX.grid.i8 (dim.x * dim.y signed bytes, cell (x, y) at x * dim.x + y) + PREFIX.grid.pgm

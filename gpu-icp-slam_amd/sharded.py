@@ -174,6 +174,11 @@ class ShardedSlam:
         and scan, no collective, the unsharded handle's bits on every rank."""
         return self.eng.register_batch(starts, **opts)
 
+    def search(self, centre=None, scores=False, **opts):
+        """Windowed correlative scan-to-map search (pfslam_search): passed through like register -- replicated map and scan, no
+        collective, the unsharded handle's bits on every rank."""
+        return self.eng.search(centre, scores, **opts)
+
     def _all_gather(self, dst, src, which):
         """Collective `which` (0 pose blocks, 1 keys, 2 weights) of the frame being enqueued, in the stream the engine names for it
         (GPU engines: pfslam_shard_stream -- stream order is all the ordering there is; gloo completes it before it returns)."""

@@ -29,6 +29,7 @@
  *   pfslam_nearest / pfslam_register   no counterpart: the exact nearest map node, and transformPointICP iterated on the device with
  *                                      its three defects optional (see pfslam_register below)
  *   pfslam_register_batch              no counterpart: pfslam_register from many start poses in one launch, and the pick of the best run
+ *   pfslam_search                      no counterpart: every pose of a window scored against a distance field of the map, the best returned
  *   pfslam_topology_update, find_walls,
  *   check_loop_closure, get_topology   UpdateTopology / FindWalls / CheckLoopClosure   kernel.cu:623-795
  *   pfslam_shard_disperse / score / weights / finish   particleFilter split where a multi-GPU caller places its three
@@ -473,6 +474,70 @@ int pfslam_register(pfslam_handle *h, const float start[3], const pfslam_registe
  * handle are replicated, so every rank gets the unsharded handle's bits. */
 int pfslam_register_batch(pfslam_handle *h, const float *starts /* m x 3 */, int m, const pfslam_register_opts *opts,
                           float *poses_out /* m x 3 */, float *info /* m x 8 */, int *best /* may be NULL */);
+/* pfslam_search: windowed correlative scan-to-map search (no reference counterpart).  Every pose of a window around `centre` is scored
+ * against a distance field of the map -- one field lookup per beam instead of a tree search -- and the best one is returned: the wide-basin
+ * start pfslam_register lacks (ICP is local, see pfslam_register_batch above), an answer to "where in this window does the scan fit best"
+ * after a bad resample, and a check of the pairs pfslam_check_loop_closure proposes.
+ *   centre    float[3], or NULL = the handle's pose (read back first, as pfslam_get_pose does: the one case with a second copy and wait)
+ *   pose_out  float[3]: the winning candidate
+ *   info      float[8] = {status, (float)k, in-range beams at the winner's heading, fdiv((float)S * u, (float)n_in), (float)S,
+ *             (float)candidates, (float)qcap, 0}; status 0 = ok, 2 = no heading has an in-range beam: pose_out is the centre and
+ *             info = {2, -1, 0, 0, 0, candidates, qcap, 0}
+ *   scores    NULL or one int32 per candidate: S(k), INT32_MAX for the candidates of a heading without an in-range beam
+ * All arithmetic is float, one rounding per operation, in the order written, no contraction, divisions (fdiv) correctly rounded.  It needs
+ * map_res_x == map_res_y; res is that resolution, (cx, cy, ct) the centre, hx, hy, ht the three halves:
+ *   unit, cap    u = (res * res) * 0.0625f           qcap = (int)rintf(fdiv(max_dist * max_dist, u)), refused unless 1 <= qcap <= 65535
+ *   field        the cell with lattice index (kx, ky) has q = min((int)rintf(fdiv(d2, u)), qcap), d2 being pfslam_nearest's d2 of the query
+ *                ((float)kx * res, (float)ky * res, 0); qcap where that query has no nearest node.  (A d2 too large for the conversion
+ *                saturates.)  The call builds the bounding box of the end-point cells of all its headings, grown by hx * stride and
+ *                hy * stride cells: every cell a candidate can touch, so there is no cell outside it to define.
+ *   candidates   k = (a * (2 hy + 1) + j) * (2 hx + 1) + i, i, j, a counted from 0
+ *                theta_a = ct + (float)(a - ht) * step_theta
+ *                x_i = cx + (float)((i - hx) * stride) * res         y_j = cy + (float)((j - hy) * stride) * res
+ *   end points   for heading a and beam b: (wx, wy) = CleanLidarScan(b, scan[b], theta_a), in = |wx| < 20 && |wy| < 20,
+ *                ex = (int)rintf(fdiv(cx + wx, res)), ey = (int)rintf(fdiv(cy + wy, res)); an in-range beam whose ex or ey is not finite or
+ *                exceeds +-2^20 counts as qcap for every candidate.  End points depend on the heading only: a translation of the window is
+ *                a pure index shift of `stride` cells, which is the point of the design.
+ *   score        S(k) = sum over the in-range beams of q[ex + (i - hx) * stride, ey + (j - hy) * stride]; integers, S <= 4096 * 65535 < 2^31:
+ *                exact in any order
+ *   result       the candidate with the smallest S, the lowest k among equal ones; a heading with no in-range beam takes no part
+ * Refused (non-zero, pfslam_last_error names the cause, outputs untouched): a NULL argument other than centre or scores; a half < 0, stride
+ * outside 1 .. 64, step_theta not finite or (half_theta > 0) not > 0, max_dist not finite or not > 0, reserved_ non-zero; qcap outside
+ * 1 .. 65535; a centre that is not finite; no map; n_beams > 4096; map_res_x != map_res_y; more than 2^24 candidates; more than 2^24 end
+ * points ((2 half_theta + 1) * n_beams); a field above 2^26 cells, bounded BEFORE the launch by
+ *     (rint((cx + 20) / res) - rint((cx - 20) / res) + 1 + 2 hx stride) * (the same in y)   (each rint held inside +-2^20):
+ * 1641 x 1641 cells for the defaults at res = 0.025.  The box a call really builds is that of its scan's end points and much smaller.
+ *   The cap of 2^24 candidates bounds one call.  Measured on one MI355X, 1081 beams, the benchmark's 100 000-point map (profiles/search.txt):
+ *   scoring takes 0.38 ms per 10^6 candidates at stride 1 and 0.36 ms at stride 2 once the window fills the device (5.5e5 candidates; the
+ *   891 waves of a default window do not: its scoring kernel takes 0.10 ms); the field kernel alone, from a kernel trace, 0.92 ms for
+ *   the 0.082 M cells of a default call there -- the launch is as long as its slowest tree searches -- and 1.6 ms for the 1.8 M cells of
+ *   the same call on a 4000-point map (0.88 ms per 10^6 cells); a whole default call of 55 473 candidates 1.06 ms; a call of 16 776 177
+ *   candidates, just under the cap, 9.0 ms.  In the 0.41 s of a full pfslam_register_batch launch (4096 rows x 40 iterations, same
+ *   map) 45 calls at the cap score 7.6e8 candidates.
+ *   Kernel resources (VGPRs / LDS bytes per workgroup / waves per SIMD): end points 94 / 80 / 5, field 18 / 0 / 8, scoring 25 / 0 / 8.
+ * What the search is for, measured with the restatement (tests/test_search_spec.py, profiles/search.txt): in pfslam_register_batch's scenario
+ * -- the scan cast from (10, -8, 0.3), where pfslam_register alone ends at the pose from 6 of the 27 starts of a +-0.4 m, +-0.15 rad grid --
+ * a window of +-0.5 m at stride 2 and +-0.2 rad at 0.0125 rad around each of the 26 off-centre starts puts the winner within one step of
+ * the pose, and pfslam_register from the winner ends within one map cell and one beam step, from 26 of 26.  Those starts lie on the
+ * window's own lattice, so the pose itself is a candidate; with every centre moved a third of a step off it in each coordinate the count
+ * is 26 of 26 again (winner 0.017 m and 0.004 rad off, 7 mm after the registration).  max_dist 0.1, 0.2 and 0.5 give the same winners: next
+ * to the pose no beam is near saturation, so this scenario does not tell them apart.
+ * Like pfslam_register it first books the frames in flight and then runs on the handle's stream, honours pfslam_set_trig, reads the handle's
+ * device-resident map and scan and writes no state another entry point reads: the field, the end points, the score volume and the result
+ * are its own buffers (they belong to the handle, grow when a call needs more and go with pfslam_destroy).  One result copy and one wait
+ * per call; the score volume is copied only when `scores` is not NULL.  The map and the scan of a sharded handle are replicated, so every
+ * rank gets the unsharded handle's bits. */
+typedef struct pfslam_search_opts {
+    int32_t half_x, half_y, half_theta; /* window: (2 hx + 1)(2 hy + 1)(2 ht + 1) candidates, each half >= 0 */
+    int32_t stride;                     /* translation step in map cells, 1 .. 64 */
+    float   step_theta;                 /* heading step (rad), finite, > 0 unless half_theta == 0 */
+    float   max_dist;                   /* saturation distance (m), finite, > 0 */
+    int32_t reserved_[2];               /* must be 0 */
+} pfslam_search_opts;
+/* {20, 20, 16, 1, 0.0125f, 0.2f, {0, 0}} */
+void pfslam_search_default_opts(pfslam_search_opts *opts);
+int pfslam_search(pfslam_handle *h, const float centre[3] /* NULL = the handle's pose */, const pfslam_search_opts *opts, float pose_out[3],
+                  float info[8], int32_t *scores /* NULL or one int per candidate */);
 /* ---- round-5 frame loop: test and measurement support (no reference counterpart) ----
  * pfslam_set_serial(h, 1): every launch of every frame on ONE stream, in the order the four chains of a frame are enqueued (what the
  * environment variable PFSLAM_SERIAL=1 sets at creation).  Results and the cell rows' bookkeeping are the same as with the chains on their
