@@ -26,7 +26,7 @@ SYMBOLS = [
     "pfslam_kd_create", "pfslam_kd_insert_list", "pfslam_kd_insert_node", "pfslam_kd_balance", "pfslam_set_timing", "pfslam_get_timers", "pfslam_resample_plan", "pfslam_resample_gather", "pfslam_maybe_balance", "pfslam_kd_size", "pfslam_topology_update", "pfslam_find_walls",
     "pfslam_check_loop_closure", "pfslam_get_topology", "pfslam_set_topology", "pfslam_get_closures", "pfslam_score_census", "pfslam_set_census", "pfslam_get_census_log", "pfslam_ubench_gather", "pfslam_plan_stats", "pfslam_cell_stats", "pfslam_kd_parallel_sort", "pfslam_kd_sort_threads", "pfslam_kd_whole_node",
     "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_estimate", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
-    "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch", "pfslam_search", "pfslam_search_default_opts",
+    "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch", "pfslam_search", "pfslam_search_default_opts", "pfslam_search_wide",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
 
@@ -165,6 +165,7 @@ def load():
     L.pfslam_search_default_opts.restype = None
     L.pfslam_search_default_opts.argtypes = [vp]
     L.pfslam_search.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.pfslam_search_wide.argtypes = [vp, vp, vp, vp, vp, vp]
     L.pfslam_debug_check_cells.argtypes = [vp, vp]
     L.pfslam_set_probe.argtypes = [vp, i32]
     L.pfslam_get_probe.argtypes = [vp, vp, i32, vp, vp]
@@ -185,6 +186,7 @@ def load():
     L.pfslam_kd_insert_list.argtypes = [vp, i32, vp, i32, i32]
     L.pfslam_kd_balance.argtypes = [vp, i32]
     L.pfslam_debug_math.argtypes = [vp, i32, vp, i32, vp]
+    L.pfslam_debug_search_frontier.argtypes = [vp, i32]
     L.pfslam_set_timing.argtypes = [vp, i32]
     L.pfslam_get_timers.argtypes = [vp, vp]
     _lib = L
@@ -635,6 +637,24 @@ class PfSlam:
         if scores:
             out["scores"] = vol
         return out
+
+    def search_wide(self, centre=None, **opts):
+        """pfslam_search's winner over windows of up to 2^31 - 1 candidates, found by branch and bound (include/pfslam.h,
+        pfslam_search_wide).  Returns search()'s dict without scores, index and candidates exact (from stats), plus stats: the eight
+        int64 {k, candidates, nodes bounded above level 0, candidates scored, top level, batches, cells of the field box, 0}."""
+        o = SearchOpts()
+        self.L.pfslam_search_default_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("half_x", "half_y", "half_theta", "stride", "step_theta", "max_dist"):
+                raise TypeError("search_wide() has no option %r" % k)
+            setattr(o, k, v)
+        pose, info, stats = np.zeros(3, np.float32), np.zeros(8, np.float32), np.zeros(8, np.int64)
+        c = None if centre is None else np.ascontiguousarray(centre, dtype=np.float32).reshape(-1)
+        if c is not None and c.shape != (3,):
+            raise ValueError("search_wide(): centre must be (x, y, theta), got %d values" % c.size)
+        _chk(self.L.pfslam_search_wide(self._h, None if c is None else _p(c), C.byref(o), _p(pose), _p(info), _p(stats)), "pfslam_search_wide")
+        return {"pose": pose, "status": int(info[0]), "index": int(stats[0]), "beams": int(info[2]), "mean_d2": float(info[3]), "score": int(info[4]),
+                "candidates": int(stats[1]), "qcap": int(info[6]), "info": info, "stats": stats}
 
     def frame_mode(self):
         out = (C.c_int * 4)()

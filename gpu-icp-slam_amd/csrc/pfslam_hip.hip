@@ -160,6 +160,14 @@ struct pfslam_handle {
     int *srch_nin = nullptr, *srch_scores = nullptr;
     unsigned long long *srch_state = nullptr;
     size_t srch_field_cap = 0, srch_ends_cap = 0, srch_nin_cap = 0, srch_scores_cap = 0;
+    // pfslam_search_wide's own buffers, grown the same way: the field and its min-pooled levels, the end points, the in-range counts, the
+    // frontier (one buffer of `wide_frontier` nodes per level), the lower bounds of one batch; key, box words, child count and result row
+    uint16_t *wide_field = nullptr;
+    int2 *wide_ends = nullptr;
+    int *wide_nin = nullptr, *wide_nodes = nullptr, *wide_lb = nullptr;
+    unsigned long long *wide_state = nullptr;
+    size_t wide_field_cap = 0, wide_ends_cap = 0, wide_nin_cap = 0, wide_nodes_cap = 0, wide_lb_cap = 0;
+    int wide_frontier = 0; // 0 = the default (pfslam_debug_search_frontier)
     float *est_part = nullptr; // pfslam_estimate: 11 tile sums per 4096-particle tile of the GLOBAL cloud, then the 16 output floats
     // grid path
     int8_t *grid = nullptr;
@@ -1040,7 +1048,7 @@ extern "C" int pfslam_destroy(pfslam_handle *h)
                     h->fit, h->fit_i, h->partial, h->mkey, h->order2, h->cells, h->stats, h->pose, h->start, h->icp_tar, h->icp_cor, h->icp_dbg,
                     h->free_mask, h->blk_cnt, h->wall_cell, h->free_cell, h->wall_pts, h->free_pts,
                     h->wall_c, h->free_c, h->counts, h->tile_r, h->tile_r2, h->sums, h->cdf,
-                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->srch_field, h->srch_ends, h->srch_nin, h->srch_scores, h->srch_state, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
+                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->srch_field, h->srch_ends, h->srch_nin, h->srch_scores, h->srch_state, h->wide_field, h->wide_ends, h->wide_nin, h->wide_nodes, h->wide_lb, h->wide_state, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (h->own_global) {
@@ -2449,3 +2457,4 @@ static int frame_v2_finish(pfslam_handle *h);
 #include "pfslam_register.hip.inc"
 #include "pfslam_register_batch.hip.inc"
 #include "pfslam_search.hip.inc"
+#include "pfslam_search_wide.hip.inc"

@@ -317,6 +317,26 @@ bool pfslamSearch(glm::vec3 centre, glm::vec3 &pose, int *index)
     if (index) *index = (int)info[1];
     return true;
 }
+bool pfslamSearchWide(glm::vec3 centre, float half_metres, float half_radians, glm::vec3 &pose, long long *index)
+{
+    if (!g_handle) return false;
+    pfslam_search_opts o;
+    pfslam_search_default_opts(&o);
+    float res = 0.025f; // pfslam_default_config
+    if (g_scene && !g_scene->maps.empty()) res = g_scene->maps[0].resolution.x;
+    o.half_x = o.half_y = (int)lrintf(half_metres / res);
+    o.half_theta = (int)floorf(half_radians / o.step_theta); // (never past the half turn asked for)
+    const float c[3] = {centre.x, centre.y, centre.z};
+    float p[3], info[8];
+    int64_t stats[8];
+    if (pfslam_search_wide(g_handle, c, &o, p, info, stats)) { // (an empty map is a state of the filter, not a failure of the program)
+        fprintf(stderr, "pfslamSearchWide: %s\n", pfslam_last_error());
+        return false;
+    }
+    pose = glm::vec3(p[0], p[1], p[2]);
+    if (index) *index = (long long)stats[0];
+    return true;
+}
 std::vector<std::pair<int, int>> pfslamLoopClosures()
 {
     std::vector<std::pair<int, int>> out;

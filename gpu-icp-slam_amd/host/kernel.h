@@ -79,6 +79,11 @@ bool pfslamRegisterBatch(const glm::vec3 *starts, int m, int max_iters, glm::vec
 // Reads the filter, changes nothing in it; like getPCData it first waits for the frames in flight.  index may be null.  false (and a
 // line on stderr): no live filter or no map yet; the outputs are then untouched.
 bool pfslamSearch(glm::vec3 centre, glm::vec3 &pose, int *index);
+// The same winner over a window too large to score candidate by candidate (include/pfslam.h, pfslam_search_wide): +-half_metres in x and
+// y at stride 1 (rounded to map cells) and +-half_radians in steps of 0.0125 rad (rounded down) around `centre`, the default max_dist;
+// found by branch and bound, exactly.  *index is the exact candidate number (it can pass 2^24, where a float rounds), -1 as above; it
+// may be null.  false (and a line on stderr): no live filter, no map yet, or a window beyond the entry point's caps.
+bool pfslamSearchWide(glm::vec3 centre, float half_metres, float half_radians, glm::vec3 &pose, long long *index);
 // Map export for an end-to-end comparison: the point-cloud map as the reference's viewer filters it
 // (nodes with w > -100, main.cpp:269-284) -> PREFIX.kd.bin (float x, y, z, w per point, in node order) + PREFIX.kd.csv, and
 // the 2-D occupancy grid -> PREFIX.grid.i8 (dim.x * dim.y signed bytes, cell (x, y) at x * dim.x + y) + PREFIX.grid.pgm

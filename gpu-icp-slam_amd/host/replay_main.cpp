@@ -1,5 +1,5 @@
 // replay_main.cpp -- headless counterpart of the reference's main loop (main.cpp:47-96, 175-229):
-//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1] [export=PREFIX]
+//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2] [export=PREFIX]
 //     grid           the 2-D occupancy-grid stages instead of the point-cloud ones
 //     loop           UpdateTopology + CheckLoopClosure at the end of every frame (kernel.cu:1750-1751, commented out in
 //                    the reference's shipped step); loop-closure proposals are printed per frame
@@ -13,6 +13,8 @@
 //                    and as float bits ("best -1" and no pose when no run completed an iteration)
 //     search=1       a further line per frame: pfslamSearch with the default window around the frame's pose: the candidate it picks and
 //                    that candidate's pose, as decimals and as float bits
+//     search=2       instead a line "search_wide ..." per frame: pfslamSearchWide over +-20 m and a full turn (+-3.14159 rad) around the
+//                    frame's pose, in the same form
 //     export=PREFIX  after the last frame: the map as the reference's viewer filters it (KD nodes with w > -100,
 //                    main.cpp:269-284) and the occupancy grid -> PREFIX.kd.bin / .kd.csv / .grid.i8 / .grid.pgm
 // iteration 0: Free + Init; then particleFilter(pbo=NULL, ++iteration, lidar) until the scans run out.
@@ -27,14 +29,14 @@
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1] [export=PREFIX]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2] [export=PREFIX]\n", argv[0]);
         return 1;
     }
     Scene *scene = new Scene(argv[1]);
     Lidar *lidar = new Lidar(argv[2]);
     size_t last = lidar->scans.size() - 1;
-    bool loop = false, estimate = false, search = false;
-    int register_iters = 0, multistart_iters = 0;
+    bool loop = false, estimate = false;
+    int register_iters = 0, multistart_iters = 0, search = 0;
     std::string export_prefix;
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "grid") == 0) pfslamUseGridMap(true);
@@ -43,7 +45,7 @@ int main(int argc, char **argv)
         else if (strncmp(argv[i], "estimate=", 9) == 0) estimate = atoi(argv[i] + 9) != 0;
         else if (strncmp(argv[i], "register=", 9) == 0) register_iters = atoi(argv[i] + 9);
         else if (strncmp(argv[i], "multistart=", 11) == 0) multistart_iters = atoi(argv[i] + 11);
-        else if (strncmp(argv[i], "search=", 7) == 0) search = atoi(argv[i] + 7) != 0;
+        else if (strncmp(argv[i], "search=", 7) == 0) search = atoi(argv[i] + 7);
         else if (strncmp(argv[i], "export=", 7) == 0) export_prefix = argv[i] + 7;
         else if (atoi(argv[i]) > 0) last = std::min(last, (size_t)atoi(argv[i]));
     }
@@ -114,7 +116,7 @@ int main(int argc, char **argv)
                 printf("multistart %zu best %d pose %.6f %.6f %.6f bits %08x %08x %08x\n", iteration, best, r.x, r.y, r.z, b[0], b[1], b[2]);
             }
         }
-        if (search) {
+        if (search == 1) {
             glm::vec3 r;
             int index = -1;
             if (pfslamSearch(pos, r, &index)) {
@@ -123,6 +125,17 @@ int main(int argc, char **argv)
                 printf("search %zu index %d pose %.6f %.6f %.6f bits %08x %08x %08x\n", iteration, index, r.x, r.y, r.z, b[0], b[1], b[2]);
             } else {
                 printf("search %zu none\n", iteration);
+            }
+        }
+        if (search == 2) {
+            glm::vec3 r;
+            long long index = -1;
+            if (pfslamSearchWide(pos, 20.0f, 3.14159f, r, &index)) {
+                unsigned int b[3];
+                memcpy(&b[0], &r.x, 4); memcpy(&b[1], &r.y, 4); memcpy(&b[2], &r.z, 4);
+                printf("search_wide %zu index %lld pose %.6f %.6f %.6f bits %08x %08x %08x\n", iteration, index, r.x, r.y, r.z, b[0], b[1], b[2]);
+            } else {
+                printf("search_wide %zu none\n", iteration);
             }
         }
     }

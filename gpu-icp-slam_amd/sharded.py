@@ -179,6 +179,10 @@ class ShardedSlam:
         collective, the unsharded handle's bits on every rank."""
         return self.eng.search(centre, scores, **opts)
 
+    def search_wide(self, centre=None, **opts):
+        """pfslam_search's winner over a window of up to 2^31 - 1 candidates (pfslam_search_wide): passed through like search."""
+        return self.eng.search_wide(centre, **opts)
+
     def _all_gather(self, dst, src, which):
         """Collective `which` (0 pose blocks, 1 keys, 2 weights) of the frame being enqueued, in the stream the engine names for it
         (GPU engines: pfslam_shard_stream -- stream order is all the ordering there is; gloo completes it before it returns)."""

@@ -30,6 +30,7 @@
  *                                      its three defects optional (see pfslam_register below)
  *   pfslam_register_batch              no counterpart: pfslam_register from many start poses in one launch, and the pick of the best run
  *   pfslam_search                      no counterpart: every pose of a window scored against a distance field of the map, the best returned
+ *   pfslam_search_wide                 no counterpart: the same winner over windows of up to 2^31 - 1 candidates, by branch and bound
  *   pfslam_topology_update, find_walls,
  *   check_loop_closure, get_topology   UpdateTopology / FindWalls / CheckLoopClosure   kernel.cu:623-795
  *   pfslam_shard_disperse / score / weights / finish   particleFilter split where a multi-GPU caller places its three
@@ -538,6 +539,51 @@ typedef struct pfslam_search_opts {
 void pfslam_search_default_opts(pfslam_search_opts *opts);
 int pfslam_search(pfslam_handle *h, const float centre[3] /* NULL = the handle's pose */, const pfslam_search_opts *opts, float pose_out[3],
                   float info[8], int32_t *scores /* NULL or one int per candidate */);
+/* pfslam_search_wide: pfslam_search's winner over windows far beyond its cap (no reference counterpart) -- "where on this map was this scan
+ * taken", at any heading: the kidnapped robot, a restart on a saved map, a loop-closure candidate checked at every heading.  +-20 m and a
+ * full turn on a 40 m map at 0.025 m are 1601 x 1601 x 503 = 1 289 290 103 candidates: 77 pfslam_search calls at the cap.
+ * Definition by reference.  The candidates k, theta_a, x_i, y_j, the end points, the field, S(k), the tie rule (the smallest S, the
+ * lowest k among equal ones; a heading with no in-range beam takes no part), pose_out, info and status 2 are pfslam_search's, word for
+ * word.  For every call pfslam_search accepts, pose_out and info are bit for bit what pfslam_search returns.  HOW the winner is found is
+ * not part of the specification (see "Method").  There is no `scores` array: the volume can pass 2^30 entries.
+ *   stats     NULL or int64[8]: info[1] = (float)k and info[5] = (float)candidates round above 2^24, so stats carries them exactly:
+ *             [0] k (-1 with status 2)   [1] candidates   [2] nodes bounded above level 0   [3] level-0 candidates scored
+ *             [4] top level used         [5] batches      [6] cells of the field box the call built   [7] 0
+ *             [2], [3] and [5] describe what the implementation did; they are not specified values.
+ * Caps: at most 2^31 - 1 candidates, so that k stays a non-negative int32 and the 64-bit key (S << 32 | k) is kept;
+ * (2 half_x + 1)(2 half_y + 1) <= 2^24; at most 2^24 end points; the field is bounded as pfslam_search's, 2^26 cells.  Every other refusal
+ * of pfslam_search applies, in the same order and with the same wording under this function's name.
+ * Method.  Candidates lie on a lattice and a translation is an index shift into one field, so the sum of the same lookups into a
+ * min-pooled copy of the field bounds S from below for a whole block of translations at once.  M_0 = q; M_L[x, y] = min of M_{L-1} at
+ * (x, y), (x + h, y), (x, y + h), (x + h, y + h), h = 2^(L-1) stride, terms outside the box skipped: the smallest q of a 2^L x 2^L block
+ * of the window's own lattice.  A node is (heading a, block origin (I, J), level L); LB = sum over the in-range beams of
+ * M_L[ex + (I - hx) stride, ey + (J - hy) stride] <= S of every candidate of the block, and = S at level 0.  The block's origin is a
+ * candidate, the block's lowest k, and its exact S is the same index into M_0: every node scored also offers its origin to the key.
+ * From the top level (the smallest L <= 7 with 2^L >= the window's longer side) down: score a level, then drop a node only if
+ * (LB << 32 | k_origin) > the key -- never on LB = S alone, which would lose the lowest-k tie -- and split the others into their up to
+ * four children inside the window.  The frontier is bounded: a level is worked through in batches of a quarter of a frontier buffer
+ * (2^22 nodes), each batch taken down to level 0 before the next, so poor pruning costs time, never the result.
+ * Memory: a call holds (top level + 1) fields of the box's size, at worst 8 x 128 MB, and (top level + 2) frontier buffers of 16 MB.
+ * Host waits: one per batch above level 0 (it reads how many children the batch left) and one for the result; a call whose levels fit a
+ * batch each makes at most top level + 1 waits, at most 8 (+ one for a NULL centre).
+ * The counts in stats[2], [3] and [5] are the same from run to run while every level fits one batch; beyond that the order in which a level's
+ * survivors were appended decides which share a batch, and the counts (never the result) can differ by a few.
+ *   Measured on one MI355X, 1081 beams, the scan cast from (10, -8, 0.3) (profiles/search_wide.txt; HIP events around whole calls): the
+ *   whole map, 1601 x 1601 x 503 = 1 289 290 103 candidates around (0, 0, 0), takes 13.3 ms on the 4000-point map (206 727 nodes bounded,
+ *   4 candidates scored, 8 batches; the field of 10.2 M cells is 10.3 ms of it, the scoring 2.5 ms, the seven pyramid levels 0.2 ms) and
+ *   14.5 ms on the benchmark's 100 000-point map (3.46 M nodes bounded, 40 candidates scored, 16 - 17 batches; field 6.4 ms, scoring 7.2 ms).
+ *   The same winner from 503 pfslam_search calls, one per heading -- the only exact way before -- takes 3622 ms and 3634 ms: 273 and 251
+ *   times as long (two runs each, 2 ms and 7 ms apart).  713 x 713 x 33, just under pfslam_search's cap: 3.0 ms and 2.4 ms against 10.3 ms
+ *   and 9.5 ms for the one pfslam_search call; 725 x 725 x 33, just above it: 3.0 ms and 2.6 ms against 91 ms and 76 ms for 33 per-heading
+ *   calls.  The default window, where the pyramid is overhead: 1.63 ms and 0.94 ms against pfslam_search's 1.48 ms and 0.82 ms.
+ *   Kernel resources (VGPRs / LDS bytes per workgroup / waves per SIMD): pyramid 9 / 0 / 8, top level 14 / 0 / 8, scoring 59 / 0 / 8 (44 at
+ *   level 0), expansion 18 / 0 / 8.
+ * Like pfslam_search it first books the frames in flight and then runs on the handle's stream, honours pfslam_set_trig, reads the handle's
+ * device-resident map and scan and writes no state another entry point reads: the fields, the end points, the frontier and the result are
+ * its own buffers (they belong to the handle, grow when a call needs more and go with pfslam_destroy).  The map and the scan of a sharded
+ * handle are replicated, so every rank gets the unsharded handle's bits. */
+int pfslam_search_wide(pfslam_handle *h, const float centre[3] /* NULL = the handle's pose */, const pfslam_search_opts *opts,
+                       float pose_out[3], float info[8], int64_t stats[8] /* may be NULL */);
 /* ---- round-5 frame loop: test and measurement support (no reference counterpart) ----
  * pfslam_set_serial(h, 1): every launch of every frame on ONE stream, in the order the four chains of a frame are enqueued (what the
  * environment variable PFSLAM_SERIAL=1 sets at creation).  Results and the cell rows' bookkeeping are the same as with the chains on their
