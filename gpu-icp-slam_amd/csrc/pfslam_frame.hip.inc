@@ -1590,7 +1590,7 @@ static int frame_v2_finish(pfslam_handle *h)
         if (c.multi) FV_EDGE_WAIT(F, PF_FL_POSEG, h->ev_poseg, 0);
         const int cx = (int)roundf(0.5f * h->dimx + h->cfg.map_res_x / 2), cy = (int)roundf(0.5f * h->dimy + h->cfg.map_res_y / 2);
         const int M = h->dimx * h->dimy, nblk = (M + 4095) / 4096;
-        if (!h->masks_cleared) HIPCHK(hipMemsetAsync(h->free_mask, 0, (size_t)2 * M, F));
+        if (!h->masks_cleared) HIPCHK(hipMemsetAsync(h->free_mask, 0, mask_bytes(h), F));
         hipLaunchKernelGGL(k_get_walls, dim3((h->nb + 3) / 4), dim3(256), 0, F, h->scan, h->nb, h->pose, cx, cy, h->free_mask, h->wall_mask, h->dimx, h->dimy,
                            h->cfg.map_res_x, h->cfg.map_res_y, 0, c.psrc, h->trig);
         hipLaunchKernelGGL(k_count_cells, dim3(nblk), dim3(256), 0, F, h->free_mask, h->wall_mask, M, h->blk_cnt);

@@ -857,6 +857,11 @@ static int dalloc(T **p, size_t count)
     HIPCHK(hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
     return 0;
 }
+// The free and the wall mask share one allocation, so one memset clears both.  k_count_cells and k_scatter_cells read them 16 bytes
+// at a time: the wall mask starts a whole number of 16-byte chunks behind the free mask, whatever dimx * dimy is.  The 16 bytes of
+// slack behind it take the wall cell whose float index (wx * dimx + wy, inexact above 4096 cells per side) rounds up to M .. M + 8.
+static size_t mask_stride(const pfslam_handle *h) { return ((size_t)h->dimx * h->dimy + 15) / 16 * 16; }
+static size_t mask_bytes(const pfslam_handle *h) { return 2 * mask_stride(h) + 16; }
 
 static pf::KdView kd_view(const pfslam_handle *h) { return pf::KdView{h->hot, h->kz, h->parent, h->kw, h->planar}; }
 static int settle(pfslam_handle *h);   // finish and book the frames in flight (pfslam_stages.hip.inc)
@@ -949,8 +954,8 @@ static int create_impl(pfslam_handle *h)
     HIPCHK(hipMemsetAsync(h->cells, 0, ((size_t)2 * PF_CELLS_MAX + PF_CELLS_MAX / 1024) * sizeof(int), h->stream));
     CHK(dalloc(&h->stats, 8)); CHK(dalloc(&h->pose, 4)); CHK(dalloc(&h->start, 4));
     CHK(dalloc(&h->icp_tar, (size_t)h->nb * 4)); CHK(dalloc(&h->icp_cor, (size_t)h->nb * 4)); CHK(dalloc(&h->icp_dbg, 64)); // (round-5 frames: two of them, by ticket parity)
-    CHK(dalloc(&h->free_mask, 2 * M)); // the two masks are contiguous: one memset per frame
-    h->wall_mask = h->free_mask + M;
+    CHK(dalloc(&h->free_mask, mask_bytes(h))); // the two masks are contiguous: one memset per frame
+    h->wall_mask = h->free_mask + mask_stride(h);
     h->max_wall = h->nb;
     h->max_free = (int)std::min<size_t>(M, (size_t)h->nb * (size_t)std::max(h->dimx, h->dimy));
     CHK(dalloc(&h->blk_cnt, 2 * ((M + 4095) / 4096) + 8));

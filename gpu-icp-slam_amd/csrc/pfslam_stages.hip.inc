@@ -1877,7 +1877,7 @@ static int fork_icp(pfslam_handle *h)
     // two more nodes that do not depend on the scores leave the chain behind the score kernel: the mask memset of the map
     // update -- only when the last map update did not leave the masks clean (k_scatter_cells wipes them) -- and the reset of
     // the min/max keys (both are only touched again after the join)
-    if (!h->masks_cleared) HIPCHK(hipMemsetAsync(h->free_mask, 0, (size_t)2 * h->dimx * h->dimy, st));
+    if (!h->masks_cleared) HIPCHK(hipMemsetAsync(h->free_mask, 0, mask_bytes(h), st));
     CHK(launch_stats_reset(h, st));
     HIPCHK(hipEventRecord(h->ev_join, st));
     h->icp_forked = true;
@@ -1924,8 +1924,7 @@ extern "C" int pfslam_icp(pfslam_handle *h, const float start[3], float pose_out
 // ---- point-cloud map update ----------------------------------------------------------------
 static int launch_walls_and_lists(pfslam_handle *h, hipStream_t st, int cx, int cy, int centre_from_pose = 0)
 {
-    const int M = h->dimx * h->dimy;
-    if (!h->masks_cleared) HIPCHK(hipMemsetAsync(h->free_mask, 0, (size_t)2 * M, st)); // free + wall masks
+    if (!h->masks_cleared) HIPCHK(hipMemsetAsync(h->free_mask, 0, mask_bytes(h), st)); // free + wall masks
     h->masks_cleared = false;
     hipLaunchKernelGGL(k_get_walls, dim3((h->nb + 3) / 4), dim3(256), 0, st, h->scan, h->nb, h->pose, cx, cy,
                        h->free_mask, h->wall_mask, h->dimx, h->dimy, h->cfg.map_res_x, h->cfg.map_res_y, centre_from_pose,

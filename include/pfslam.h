@@ -66,7 +66,10 @@ typedef struct pfslam_config {
     float map_scale_x, map_scale_y; /* Patch.scale (data/map_settings.txt: 40 40) */
     float map_res_x, map_res_y;     /* Patch.resolution (0.025).  int(scale / res) must be the same in x and y: the
                                      * reference indexes cell (x, y) as x * dim.x + y (kernel.cu:120, 539, 1438), which is
-                                     * only well defined on a square grid; pfslam_create refuses anything else */
+                                     * only well defined on a square grid; pfslam_create refuses anything else.  The rays' cells
+                                     * come from a closed form of the reference's Bresenham walk whose product k * deltay is 32-bit:
+                                     * it is exact while a ray is shorter than 46 341 cells, that is while 20 m / res stays below
+                                     * that (res above about 0.43 mm) */
     int32_t kd_capacity;   /* KD_MAX_SIZE (kernel.cu:77); nodes, at most 2^27 - 1.  A frame whose new walls do not fit inserts
                             * none of them and fails ("kd_capacity exhausted"; reported by the call that books the frame, see
                             * pfslam_step) -- the reference has no bound check at all */
