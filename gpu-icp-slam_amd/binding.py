@@ -27,6 +27,7 @@ SYMBOLS = [
     "pfslam_check_loop_closure", "pfslam_get_topology", "pfslam_set_topology", "pfslam_get_closures", "pfslam_score_census", "pfslam_set_census", "pfslam_get_census_log", "pfslam_ubench_gather", "pfslam_plan_stats", "pfslam_cell_stats", "pfslam_kd_parallel_sort", "pfslam_kd_sort_threads", "pfslam_kd_whole_node",
     "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_estimate", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
     "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch", "pfslam_search", "pfslam_search_default_opts", "pfslam_search_wide",
+    "pfslam_search_best", "pfslam_search_best_default_opts",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
 
@@ -51,6 +52,11 @@ class SearchOpts(C.Structure):
     """pfslam_search_opts (include/pfslam.h)."""
     _fields_ = [("half_x", C.c_int32), ("half_y", C.c_int32), ("half_theta", C.c_int32), ("stride", C.c_int32),
                 ("step_theta", C.c_float), ("max_dist", C.c_float), ("reserved_", C.c_int32 * 2)]
+
+
+class BestOpts(C.Structure):
+    """pfslam_best_opts (include/pfslam.h)."""
+    _fields_ = [("count", C.c_int32), ("tile_log2", C.c_int32), ("group_theta", C.c_int32), ("reserved_", C.c_int32)]
 
 
 REGISTER_STATUS = {0: "max_iters", 1: "converged", 2: "too_few_pairs", 3: "not_finite"}
@@ -166,6 +172,9 @@ def load():
     L.pfslam_search_default_opts.argtypes = [vp]
     L.pfslam_search.argtypes = [vp, vp, vp, vp, vp, vp]
     L.pfslam_search_wide.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.pfslam_search_best_default_opts.restype = None
+    L.pfslam_search_best_default_opts.argtypes = [vp]
+    L.pfslam_search_best.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pfslam_debug_check_cells.argtypes = [vp, vp]
     L.pfslam_set_probe.argtypes = [vp, i32]
     L.pfslam_get_probe.argtypes = [vp, vp, i32, vp, vp]
@@ -655,6 +664,30 @@ class PfSlam:
         _chk(self.L.pfslam_search_wide(self._h, None if c is None else _p(c), C.byref(o), _p(pose), _p(info), _p(stats)), "pfslam_search_wide")
         return {"pose": pose, "status": int(info[0]), "index": int(stats[0]), "beams": int(info[2]), "mean_d2": float(info[3]), "score": int(info[4]),
                 "candidates": int(stats[1]), "qcap": int(info[6]), "info": info, "stats": stats}
+
+    def search_best(self, centre=None, count=8, tile_log2=3, group_theta=8, **opts):
+        """The best candidate of each of the `count` best cells of a search window (include/pfslam.h, pfslam_search_best): a cell is a tile of
+        2^tile_log2 x 2^tile_log2 translations times group_theta consecutive headings.  The window's options are search()'s.  Returns poses
+        (found, 3), info (found, 8), index (int64, the rows' k), score and beams per row, found and stats: pfslam_search_wide's eight int64
+        with the number of cells in [7].  Row 0 is search_wide()'s winner; the rows are register_batch()'s `starts`."""
+        o = SearchOpts()
+        self.L.pfslam_search_default_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("half_x", "half_y", "half_theta", "stride", "step_theta", "max_dist"):
+                raise TypeError("search_best() has no option %r" % k)
+            setattr(o, k, v)
+        b = BestOpts(int(count), int(tile_log2), int(group_theta), 0)
+        rows = min(max(int(count), 1), 64)
+        poses, info, index = np.zeros((rows, 3), np.float32), np.zeros((rows, 8), np.float32), np.zeros(rows, np.int64)
+        stats, found = np.zeros(8, np.int64), C.c_int(0)
+        c = None if centre is None else np.ascontiguousarray(centre, dtype=np.float32).reshape(-1)
+        if c is not None and c.shape != (3,):
+            raise ValueError("search_best(): centre must be (x, y, theta), got %d values" % c.size)
+        _chk(self.L.pfslam_search_best(self._h, None if c is None else _p(c), C.byref(o), C.byref(b), _p(poses), _p(info), _p(index), C.byref(found),
+                                       _p(stats)), "pfslam_search_best")
+        n = int(found.value)
+        return {"poses": poses[:n].copy(), "info": info[:n].copy(), "index": index[:n].copy(), "score": info[:n, 4].astype(np.int64),
+                "beams": info[:n, 2].astype(np.int32), "found": n, "stats": stats}
 
     def frame_mode(self):
         out = (C.c_int * 4)()

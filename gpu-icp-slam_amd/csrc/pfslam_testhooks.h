@@ -12,7 +12,7 @@ extern "C" {
  * which: 0 sincos (out: n x {sin, cos}), 1 erfcinv, 2 asin, 3 rsqrt, 4 sqrt_rn, 5 x / 0.025f,
  *        6 sub-cell index of x on the 0.025 m lattice (out: n x {sub_index, sub_index_fast or INT_MIN when not safe}, int bits) */
 int pfslam_debug_math(pfslam_handle *h, int which, const float *in_host, int n, float *out_host);
-/* pfslam_search_wide's frontier buffers hold `nodes` nodes each from the next call on (0 = the default, 2^22; at least 4), so that a small
+/* pfslam_search_wide's and pfslam_search_best's frontier buffers hold `nodes` nodes each from the next call on (0 = the default, 2^22; at least 4), so that a small
  * window is cut into many batches.  Results do not depend on it. */
 int pfslam_debug_search_frontier(pfslam_handle *h, int nodes);
 #ifdef __cplusplus

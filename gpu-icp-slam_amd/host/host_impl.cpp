@@ -337,6 +337,32 @@ bool pfslamSearchWide(glm::vec3 centre, float half_metres, float half_radians, g
     if (index) *index = (long long)stats[0];
     return true;
 }
+int pfslamSearchBest(glm::vec3 centre, float half_metres, float half_radians, int count, glm::vec3 *poses, long long *index)
+{
+    if (!g_handle || !poses) return -1;
+    pfslam_search_opts o;
+    pfslam_search_default_opts(&o);
+    pfslam_best_opts b;
+    pfslam_search_best_default_opts(&b);
+    b.count = count;
+    float res = 0.025f; // pfslam_default_config
+    if (g_scene && !g_scene->maps.empty()) res = g_scene->maps[0].resolution.x;
+    o.half_x = o.half_y = (int)lrintf(half_metres / res); // pfslamSearchWide's window
+    o.half_theta = (int)floorf(half_radians / o.step_theta);
+    const float c[3] = {centre.x, centre.y, centre.z};
+    float p[64 * 3], info[64 * 8];
+    int64_t k[64], stats[8];
+    int found = 0;
+    if (pfslam_search_best(g_handle, c, &o, &b, p, info, k, &found, stats)) { // (an empty map is a state of the filter, not a failure of the program)
+        fprintf(stderr, "pfslamSearchBest: %s\n", pfslam_last_error());
+        return -1;
+    }
+    for (int r = 0; r < found; r++) {
+        poses[r] = glm::vec3(p[3 * r], p[3 * r + 1], p[3 * r + 2]);
+        if (index) index[r] = (long long)k[r];
+    }
+    return found;
+}
 std::vector<std::pair<int, int>> pfslamLoopClosures()
 {
     std::vector<std::pair<int, int>> out;

@@ -84,6 +84,12 @@ bool pfslamSearch(glm::vec3 centre, glm::vec3 &pose, int *index);
 // found by branch and bound, exactly.  *index is the exact candidate number (it can pass 2^24, where a float rounds), -1 as above; it
 // may be null.  false (and a line on stderr): no live filter, no map yet, or a window beyond the entry point's caps.
 bool pfslamSearchWide(glm::vec3 centre, float half_metres, float half_radians, glm::vec3 &pose, long long *index);
+// The best candidate of each of the `count` (1 .. 64) best cells of pfslamSearchWide's window (include/pfslam.h, pfslam_search_best; the
+// default cells: tiles of 8 x 8 translations, groups of 8 headings): poses[r] and index[r] in ascending key order, row 0 pfslamSearchWide's
+// winner -- the starts pfslamRegisterBatch takes when one pose is not enough.  Returns the rows found (fewer than `count` only when fewer
+// cells hold a candidate, 0 when no heading has an in-range beam), or -1 (and a line on stderr): no live filter, no map yet, a count or a
+// window beyond the entry point's caps; the outputs are then untouched.  index may be null.
+int pfslamSearchBest(glm::vec3 centre, float half_metres, float half_radians, int count, glm::vec3 *poses, long long *index);
 // Map export for an end-to-end comparison: the point-cloud map as the reference's viewer filters it
 // (nodes with w > -100, main.cpp:269-284) -> PREFIX.kd.bin (float x, y, z, w per point, in node order) + PREFIX.kd.csv, and
 // the 2-D occupancy grid -> PREFIX.grid.i8 (dim.x * dim.y signed bytes, cell (x, y) at x * dim.x + y) + PREFIX.grid.pgm

@@ -1,5 +1,5 @@
 // replay_main.cpp -- headless counterpart of the reference's main loop (main.cpp:47-96, 175-229):
-//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2] [export=PREFIX]
+//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [export=PREFIX]
 //     grid           the 2-D occupancy-grid stages instead of the point-cloud ones
 //     loop           UpdateTopology + CheckLoopClosure at the end of every frame (kernel.cu:1750-1751, commented out in
 //                    the reference's shipped step); loop-closure proposals are printed per frame
@@ -15,6 +15,8 @@
 //                    that candidate's pose, as decimals and as float bits
 //     search=2       instead a line "search_wide ..." per frame: pfslamSearchWide over +-20 m and a full turn (+-3.14159 rad) around the
 //                    frame's pose, in the same form
+//     search=3       instead the lines "search_best <frame> <row> index <k> pose ... bits ..." per frame, one per row: pfslamSearchBest over the
+//                    same window, eight rows wanted ("search_best <frame> none" when the call fails or finds no row)
 //     export=PREFIX  after the last frame: the map as the reference's viewer filters it (KD nodes with w > -100,
 //                    main.cpp:269-284) and the occupancy grid -> PREFIX.kd.bin / .kd.csv / .grid.i8 / .grid.pgm
 // iteration 0: Free + Init; then particleFilter(pbo=NULL, ++iteration, lidar) until the scans run out.
@@ -29,7 +31,7 @@
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2] [export=PREFIX]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [export=PREFIX]\n", argv[0]);
         return 1;
     }
     Scene *scene = new Scene(argv[1]);
@@ -137,6 +139,17 @@ int main(int argc, char **argv)
             } else {
                 printf("search_wide %zu none\n", iteration);
             }
+        }
+        if (search == 3) {
+            glm::vec3 r[8];
+            long long index[8];
+            const int found = pfslamSearchBest(pos, 20.0f, 3.14159f, 8, r, index);
+            for (int n = 0; n < found; n++) {
+                unsigned int b[3];
+                memcpy(&b[0], &r[n].x, 4); memcpy(&b[1], &r[n].y, 4); memcpy(&b[2], &r[n].z, 4);
+                printf("search_best %zu %d index %lld pose %.6f %.6f %.6f bits %08x %08x %08x\n", iteration, n, index[n], r[n].x, r[n].y, r[n].z, b[0], b[1], b[2]);
+            }
+            if (found <= 0) printf("search_best %zu none\n", iteration);
         }
     }
     printf("mean step+readback %.3f ms over %zu frames\n", iteration ? total_ms / iteration : 0.0, iteration);

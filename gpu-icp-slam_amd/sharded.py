@@ -183,6 +183,11 @@ class ShardedSlam:
         """pfslam_search's winner over a window of up to 2^31 - 1 candidates (pfslam_search_wide): passed through like search."""
         return self.eng.search_wide(centre, **opts)
 
+    def search_best(self, centre=None, count=8, tile_log2=3, group_theta=8, **opts):
+        """The best candidate of each of the `count` best cells of a search window (pfslam_search_best): passed through like search_wide --
+        the map and the scan are replicated, so every rank gets the unsharded bits with no collective."""
+        return self.eng.search_best(centre, count=count, tile_log2=tile_log2, group_theta=group_theta, **opts)
+
     def _all_gather(self, dst, src, which):
         """Collective `which` (0 pose blocks, 1 keys, 2 weights) of the frame being enqueued, in the stream the engine names for it
         (GPU engines: pfslam_shard_stream -- stream order is all the ordering there is; gloo completes it before it returns)."""

@@ -31,6 +31,7 @@
  *   pfslam_register_batch              no counterpart: pfslam_register from many start poses in one launch, and the pick of the best run
  *   pfslam_search                      no counterpart: every pose of a window scored against a distance field of the map, the best returned
  *   pfslam_search_wide                 no counterpart: the same winner over windows of up to 2^31 - 1 candidates, by branch and bound
+ *   pfslam_search_best                 no counterpart: the best candidate of each of the N best cells of such a window, by the same descent
  *   pfslam_topology_update, find_walls,
  *   check_loop_closure, get_topology   UpdateTopology / FindWalls / CheckLoopClosure   kernel.cu:623-795
  *   pfslam_shard_disperse / score / weights / finish   particleFilter split where a multi-GPU caller places its three
@@ -587,6 +588,68 @@ int pfslam_search(pfslam_handle *h, const float centre[3] /* NULL = the handle's
  * handle are replicated, so every rank gets the unsharded handle's bits. */
 int pfslam_search_wide(pfslam_handle *h, const float centre[3] /* NULL = the handle's pose */, const pfslam_search_opts *opts,
                        float pose_out[3], float info[8], int64_t stats[8] /* may be NULL */);
+/* pfslam_search_best: the N best separated poses of a search window (no reference counterpart) -- the best candidate of each of the N best
+ * REGIONS of the window, because the N smallest scores alone all sit next to the winner.  Corridors, repeated rooms and a short scan give
+ * several basins with nearly equal scores, and the global minimum of a saturated, quantised score can be the wrong one: the rows are what
+ * pfslam_register_batch takes as `starts`, and what a particle filter is seeded with.  As wide as pfslam_search_wide, and exact.
+ * Definition by reference.  The candidates k = (a * ny + j) * nx + i, theta_a, x_i, y_j, the end points, the field, S(k) and the rule that a
+ * heading with no in-range beam takes no part are pfslam_search's, word for word (nx = 2 half_x + 1, ny, na likewise).
+ *   key              of a candidate: S(k) << 32 | k.  Keys are distinct, so their order is total.
+ *   cells            the candidates are partitioned: with Ls = tile_log2 and G = group_theta, candidate (a, j, i) belongs to cell
+ *                    ((a / G) * ty + (j >> Ls)) * tx + (i >> Ls), tx = ((nx - 1) >> Ls) + 1, ty likewise, ceil(na / G) heading groups.  A tile is
+ *                    2^Ls x 2^Ls translations of the window's own lattice, counted from i = 0, j = 0 (the alignment of the blocks
+ *                    pfslam_search_wide descends through); a group is G consecutive headings.
+ *   representative   of a cell: the smallest key among its candidates that take part; a cell without one has none.
+ *   result           the `count` cells with the smallest representatives, in ascending key order.  *found = the rows written, smaller than
+ *                    `count` only when fewer cells have a representative.  Row r: index[r] = k_r, exact; poses_out[3 r ..] the pose of k_r;
+ *                    info[8 r ..] = {0, (float)k_r, n_in of its heading, fdiv((float)S * u, (float)n_in), (float)S, (float)candidates,
+ *                    (float)qcap, 0}: pfslam_search's info for that candidate.  Rows beyond *found are left untouched.  When no heading has
+ *                    an in-range beam the call succeeds with *found = 0 and writes no row.
+ *   stats            NULL or int64[8], pfslam_search_wide's: [0] k of row 0 (-1 with no row) [1] candidates [2] nodes bounded above level 0
+ *                    [3] level-0 candidates scored [4] top level used [5] batches [6] cells of the field box [7] the cells of the call.
+ *                    [2], [3] and [5] describe what the implementation did; they are not specified values.
+ * Consequences.  Row 0 is pfslam_search_wide's winner bit for bit, for every tile_log2 and group_theta.  With count = 1, pose and info equal
+ * pfslam_search_wide's on every call both functions accept.  The separation is by partition, not by distance: two rows can be neighbours
+ * across a tile border.  A caller who wants one row per basin refines the rows with pfslam_register_batch, where they converge.
+ * Refused (non-zero, pfslam_last_error names the cause, outputs untouched): everything pfslam_search_wide refuses, in its order and wording
+ * under this function's name; then a NULL best, poses_out, info, index or found; count outside 1 .. 64; tile_log2 outside 0 .. 7;
+ * group_theta < 1; reserved_ non-zero; more than 2^22 cells, which bounds the table of representatives to 32 MB (the whole map at the
+ * defaults is 201 x 201 x 63 = 2 545 263 cells).
+ * Method.  pfslam_search_wide's descent (the same pyramid, nodes, batches of a quarter of a frontier buffer and one host wait per batch;
+ * the test hook that shrinks its frontier shrinks this one too) over a table T of one key per cell, all ones at the start.  Every node scored
+ * offers its origin's exact key to T[cell of the origin] with a 64-bit atomicMin, and to the minimum of the cell's slice (cell c lies in
+ * slice c mod 4096).  After a batch's scoring launch one workgroup selects thr, the count-th smallest of the 4096 slice minima (all ones
+ * with fewer set): entries of T only fall and the minima of different slices belong to different cells, so thr bounds the final count-th
+ * smallest representative from above.  A node with key nk = LB << 32 | k_origin is dropped (1) if nk > thr, or (2) if L <= Ls -- its block
+ * then lies inside one cell -- and nk > T[that cell].  Equality never drops a node, as in pfslam_search_wide.  At the end the cells with
+ * T <= thr are compacted, copied (the list has room for every cell, so a long list costs a copy, never the result) and sorted on the
+ * host; a last kernel fills the rows.  Memory beyond pfslam_search_wide's: 16 bytes a cell.  Host waits: pfslam_search_wide's, + 2.
+ *   Measured on one MI355X, 1081 beams, the scan cast from (10, -8, 0.3) (profiles/search_best.txt; HIP events around whole calls):
+ *   the whole map, 1601 x 1601 x 503 candidates in 201 x 201 x 63 = 2 545 263 cells around (0, 0, 0), at the defaults (count 8) takes 15.2 ms
+ *   on the 4000-point map (344 545 nodes bounded, 64 candidates scored, 8 batches) and 19.0 ms on the benchmark's 100 000-point map (5.19 M
+ *   nodes bounded, 1012 candidates scored, 24 batches), beside pfslam_search_wide's 13.1 ms and 14.5 ms in the same process: 1.16 and 1.31
+ *   times as long.  The same eight rows the only other exact way -- 503 pfslam_search calls with their volumes copied back and the cells
+ *   reduced on the host -- take 14.2 s and 8.7 s of wall clock: 930 and 459 times as long.  count = 1: 13.3 ms and 14.9 ms, 1.01 and 1.02
+ *   times pfslam_search_wide (the same nodes); count = 64: 22.2 ms and 24.6 ms, 1.69 times.  713 x 713 x 33: 3.2 ms and 2.8 ms against
+ *   pfslam_search_wide's 3.0 ms and 2.4 ms; 725 x 725 x 33: 3.3 ms and 2.9 ms against 3.1 ms and 2.6 ms; the default window: 1.79 ms and
+ *   1.10 ms against 1.64 ms and 0.96 ms.
+ *   Kernel resources (VGPRs / LDS bytes per workgroup / waves per SIMD): scoring 59 / 0 / 8 (44 at level 0), threshold 26 / 34 944 / 4 (one
+ *   workgroup a launch), expansion 19 / 0 / 8, compaction 5 / 0 / 8, rows 16 / 0 / 8.
+ * Like pfslam_search_wide it first books the frames in flight and then runs on the handle's stream, honours pfslam_set_trig, reads the
+ * handle's device-resident map and scan and writes no state another entry point reads: the fields, end points and frontier are
+ * pfslam_search_wide's scratch, the table, the list and the rows its own buffers (they belong to the handle, grow when a call needs more and
+ * go with pfslam_destroy).  The map and the scan of a sharded handle are replicated, so every rank gets the unsharded handle's bits. */
+typedef struct pfslam_best_opts {
+    int32_t count;        /* rows wanted, 1 .. 64 */
+    int32_t tile_log2;    /* Ls, 0 .. 7: a tile is 2^Ls x 2^Ls translations of the window's own lattice */
+    int32_t group_theta;  /* G >= 1: a group is G consecutive headings */
+    int32_t reserved_;    /* must be 0 */
+} pfslam_best_opts;
+/* {8, 3, 8, 0} */
+void pfslam_search_best_default_opts(pfslam_best_opts *opts);
+int pfslam_search_best(pfslam_handle *h, const float centre[3] /* NULL = the handle's pose */, const pfslam_search_opts *opts,
+                       const pfslam_best_opts *best, float *poses_out /* count x 3 */, float *info /* count x 8 */,
+                       int64_t *index /* count */, int *found, int64_t stats[8] /* may be NULL */);
 /* ---- round-5 frame loop: test and measurement support (no reference counterpart) ----
  * pfslam_set_serial(h, 1): every launch of every frame on ONE stream, in the order the four chains of a frame are enqueued (what the
  * environment variable PFSLAM_SERIAL=1 sets at creation).  Results and the cell rows' bookkeeping are the same as with the chains on their
