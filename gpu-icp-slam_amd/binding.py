@@ -26,7 +26,7 @@ SYMBOLS = [
     "pfslam_kd_create", "pfslam_kd_insert_list", "pfslam_kd_insert_node", "pfslam_kd_balance", "pfslam_set_timing", "pfslam_get_timers", "pfslam_resample_plan", "pfslam_resample_gather", "pfslam_maybe_balance", "pfslam_kd_size", "pfslam_topology_update", "pfslam_find_walls",
     "pfslam_check_loop_closure", "pfslam_get_topology", "pfslam_set_topology", "pfslam_get_closures", "pfslam_score_census", "pfslam_set_census", "pfslam_get_census_log", "pfslam_ubench_gather", "pfslam_plan_stats", "pfslam_cell_stats", "pfslam_kd_parallel_sort", "pfslam_kd_sort_threads", "pfslam_kd_whole_node",
     "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_estimate", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
-    "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch", "pfslam_search", "pfslam_search_default_opts", "pfslam_search_wide",
+    "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch", "pfslam_search", "pfslam_search_default_opts", "pfslam_search_scan", "pfslam_search_wide",
     "pfslam_search_best", "pfslam_search_best_default_opts",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
@@ -171,6 +171,7 @@ def load():
     L.pfslam_search_default_opts.restype = None
     L.pfslam_search_default_opts.argtypes = [vp]
     L.pfslam_search.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.pfslam_search_scan.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pfslam_search_wide.argtypes = [vp, vp, vp, vp, vp, vp]
     L.pfslam_search_best_default_opts.restype = None
     L.pfslam_search_best_default_opts.argtypes = [vp]
@@ -643,6 +644,41 @@ class PfSlam:
         _chk(self.L.pfslam_search(self._h, None if c is None else _p(c), C.byref(o), _p(pose), _p(info), None if vol is None else _p(vol)), "pfslam_search")
         out = {"pose": pose, "status": int(info[0]), "index": int(info[1]), "beams": int(info[2]), "mean_d2": float(info[3]), "score": int(info[4]),
                "candidates": int(info[5]), "qcap": int(info[6]), "info": info}
+        if scores:
+            out["scores"] = vol
+        return out
+
+    def search_scan(self, ref_scan, ref_pose=None, scan=None, centre=None, scores=False, **opts):
+        """Correlative scan-to-scan search (include/pfslam.h, pfslam_search_scan): search()'s window around `centre` (None: ref_pose) scored
+        against a distance field built from the end points of `ref_scan` taken at `ref_pose` (None: (0, 0, 0)); `scan` is the scan that is
+        searched (None: the handle's scan).  No map is needed.  Options and the returned dict are search()'s, plus points: the reference
+        beams in range.  Reads the handle's scan at most, writes none of its state."""
+        o = SearchOpts()
+        self.L.pfslam_search_default_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("half_x", "half_y", "half_theta", "stride", "step_theta", "max_dist"):
+                raise TypeError("search_scan() has no option %r" % k)
+            setattr(o, k, v)
+        pose, info = np.zeros(3, np.float32), np.zeros(8, np.float32)
+        ref = np.ascontiguousarray(ref_scan, dtype=np.float32).reshape(-1)
+        sc = None if scan is None else np.ascontiguousarray(scan, dtype=np.float32).reshape(-1)
+        for name, a in (("ref_scan", ref), ("scan", sc)):
+            if a is not None and len(a) != self.nb:
+                raise ValueError("search_scan(): %s must hold n_beams = %d ranges, got %d" % (name, self.nb, len(a)))
+        rp = None if ref_pose is None else np.ascontiguousarray(ref_pose, dtype=np.float32).reshape(-1)
+        c = None if centre is None else np.ascontiguousarray(centre, dtype=np.float32).reshape(-1)
+        for name, a in (("ref_pose", rp), ("centre", c)):
+            if a is not None and a.shape != (3,):
+                raise ValueError("search_scan(): %s must be (x, y, theta), got %d values" % (name, a.size))
+        vol = None
+        if scores:
+            shape = tuple(2 * max(int(v), 0) + 1 for v in (o.half_theta, o.half_y, o.half_x))
+            if shape[0] * shape[1] * shape[2] <= 1 << 24:     # (a larger window is the library's to refuse)
+                vol = np.zeros(shape, np.int32)
+        opt = lambda a: None if a is None else _p(a)
+        _chk(self.L.pfslam_search_scan(self._h, _p(ref), opt(rp), opt(sc), opt(c), C.byref(o), _p(pose), _p(info), opt(vol)), "pfslam_search_scan")
+        out = {"pose": pose, "status": int(info[0]), "index": int(info[1]), "beams": int(info[2]), "mean_d2": float(info[3]), "score": int(info[4]),
+               "candidates": int(info[5]), "qcap": int(info[6]), "points": int(info[7]), "info": info}
         if scores:
             out["scores"] = vol
         return out

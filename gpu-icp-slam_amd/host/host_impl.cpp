@@ -317,6 +317,27 @@ bool pfslamSearch(glm::vec3 centre, glm::vec3 &pose, int *index)
     if (index) *index = (int)info[1];
     return true;
 }
+bool pfslamSearchScan(const float *ref_scan, glm::vec3 ref_pose, glm::vec3 &pose, int *index, const float *scan)
+{
+    if (!g_handle) return false;
+    pfslam_search_opts o;
+    pfslam_search_default_opts(&o);
+    const float r[3] = {ref_pose.x, ref_pose.y, ref_pose.z};
+    float p[3], info[8];
+    if (pfslam_search_scan(g_handle, ref_scan, r, scan, nullptr, &o, p, info, nullptr)) {
+        fprintf(stderr, "pfslamSearchScan: %s\n", pfslam_last_error());
+        return false;
+    }
+    pose = glm::vec3(p[0], p[1], p[2]);
+    if (index) *index = (int)info[1];
+    return true;
+}
+void pfslamShiftParticles(glm::vec3 delta)
+{
+    if (!g_handle) return;
+    const float d[3] = {delta.x, delta.y, delta.z};
+    PFCHK(pfslam_shift_particles(g_handle, d), "pfslamShiftParticles");
+}
 bool pfslamSearchWide(glm::vec3 centre, float half_metres, float half_radians, glm::vec3 &pose, long long *index)
 {
     if (!g_handle) return false;

@@ -79,6 +79,15 @@ bool pfslamRegisterBatch(const glm::vec3 *starts, int m, int max_iters, glm::vec
 // Reads the filter, changes nothing in it; like getPCData it first waits for the frames in flight.  index may be null.  false (and a
 // line on stderr): no live filter or no map yet; the outputs are then untouched.
 bool pfslamSearch(glm::vec3 centre, glm::vec3 &pose, int *index);
+// Correlative scan-to-scan search (no reference counterpart; include/pfslam.h, pfslam_search_scan): the default window around `ref_pose`
+// scored against a distance field built from the end points of `ref_scan` (1081 ranges) taken at `ref_pose` -- no map is needed.  The scan
+// that is searched is `scan` (1081 ranges), or with scan == nullptr the live filter's scan (the last frame's).  pose is the best candidate,
+// *index its number (-1: no heading has an in-range beam, pose is ref_pose); pose - ref_pose is the delta pfslamShiftParticles takes.
+// Reads the filter, changes nothing in it; like getPCData it first waits for the frames in flight.  index may be null.  false (and a line
+// on stderr): no live filter or a null ref_scan; the outputs are then untouched.
+bool pfslamSearchScan(const float *ref_scan, glm::vec3 ref_pose, glm::vec3 &pose, int *index, const float *scan = nullptr);
+// The odometry hook (include/pfslam.h, pfslam_shift_particles): every particle and the robot's pose += delta.
+void pfslamShiftParticles(glm::vec3 delta);
 // The same winner over a window too large to score candidate by candidate (include/pfslam.h, pfslam_search_wide): +-half_metres in x and
 // y at stride 1 (rounded to map cells) and +-half_radians in steps of 0.0125 rad (rounded down) around `centre`, the default max_dist;
 // found by branch and bound, exactly.  *index is the exact candidate number (it can pass 2^24, where a float rounds), -1 as above; it

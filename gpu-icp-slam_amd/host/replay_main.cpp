@@ -1,5 +1,5 @@
 // replay_main.cpp -- headless counterpart of the reference's main loop (main.cpp:47-96, 175-229):
-//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [export=PREFIX]
+//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [export=PREFIX]
 //     grid           the 2-D occupancy-grid stages instead of the point-cloud ones
 //     loop           UpdateTopology + CheckLoopClosure at the end of every frame (kernel.cu:1750-1751, commented out in
 //                    the reference's shipped step); loop-closure proposals are printed per frame
@@ -17,6 +17,10 @@
 //                    frame's pose, in the same form
 //     search=3       instead the lines "search_best <frame> <row> index <k> pose ... bits ..." per frame, one per row: pfslamSearchBest over the
 //                    same window, eight rows wanted ("search_best <frame> none" when the call fails or finds no row)
+//     odometry=1     lidar-only odometry: before every frame after the first, pfslamSearchScan of the new scan against the previous scan at
+//                    the previous frame's pose (the default window around it); a line "odometry <frame> index <k> delta <dx dy dtheta> bits
+//                    <3 hex words of the winning pose>" and pfslamShiftParticles with that delta before the step ("odometry <frame> none"
+//                    and no shift when the call fails or no heading has an in-range beam)
 //     export=PREFIX  after the last frame: the map as the reference's viewer filters it (KD nodes with w > -100,
 //                    main.cpp:269-284) and the occupancy grid -> PREFIX.kd.bin / .kd.csv / .grid.i8 / .grid.pgm
 // iteration 0: Free + Init; then particleFilter(pbo=NULL, ++iteration, lidar) until the scans run out.
@@ -31,7 +35,7 @@
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [export=PREFIX]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [export=PREFIX]\n", argv[0]);
         return 1;
     }
     Scene *scene = new Scene(argv[1]);
@@ -39,6 +43,7 @@ int main(int argc, char **argv)
     size_t last = lidar->scans.size() - 1;
     bool loop = false, estimate = false;
     int register_iters = 0, multistart_iters = 0, search = 0;
+    bool odometry = false;
     std::string export_prefix;
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "grid") == 0) pfslamUseGridMap(true);
@@ -48,6 +53,7 @@ int main(int argc, char **argv)
         else if (strncmp(argv[i], "register=", 9) == 0) register_iters = atoi(argv[i] + 9);
         else if (strncmp(argv[i], "multistart=", 11) == 0) multistart_iters = atoi(argv[i] + 11);
         else if (strncmp(argv[i], "search=", 7) == 0) search = atoi(argv[i] + 7);
+        else if (strncmp(argv[i], "odometry=", 9) == 0) odometry = atoi(argv[i] + 9) != 0;
         else if (strncmp(argv[i], "export=", 7) == 0) export_prefix = argv[i] + 7;
         else if (atoi(argv[i]) > 0) last = std::min(last, (size_t)atoi(argv[i]));
     }
@@ -56,8 +62,22 @@ int main(int argc, char **argv)
     pfslamUseTopology(loop);
     double total_ms = 0;
     size_t iteration = 0, proposals = 0;
+    glm::vec3 last_pose(0.0f);
     while (iteration < last) {
         iteration++;
+        if (odometry && iteration > 1) {
+            glm::vec3 r;
+            int index = -1;
+            if (pfslamSearchScan(lidar->scans[iteration - 1].data(), last_pose, r, &index, lidar->scans[iteration].data()) && index >= 0) {
+                const glm::vec3 d(r.x - last_pose.x, r.y - last_pose.y, r.z - last_pose.z);
+                unsigned int b[3];
+                memcpy(&b[0], &r.x, 4); memcpy(&b[1], &r.y, 4); memcpy(&b[2], &r.z, 4);
+                printf("odometry %zu index %d delta %.6f %.6f %.6f bits %08x %08x %08x\n", iteration, index, d.x, d.y, d.z, b[0], b[1], b[2]);
+                pfslamShiftParticles(d);
+            } else {
+                printf("odometry %zu none\n", iteration);
+            }
+        }
         auto t0 = std::chrono::steady_clock::now();
         particleFilter(nullptr, (int)iteration, lidar);
         Particle *p; MAP_TYPE *map; KDTree::Node *kd; int np, nkd; glm::vec3 pos;
@@ -65,6 +85,7 @@ int main(int argc, char **argv)
         total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         unsigned int bx, by, bt;
         memcpy(&bx, &pos.x, 4); memcpy(&by, &pos.y, 4); memcpy(&bt, &pos.z, 4);
+        last_pose = pos;
         printf("frame %zu pose %.6f %.6f %.6f bits %08x %08x %08x particles %d kd %d", iteration, pos.x, pos.y, pos.z, bx, by, bt, np, nkd);
         if (loop) {
             const auto pairs = pfslamLoopClosures();

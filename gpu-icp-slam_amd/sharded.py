@@ -179,6 +179,11 @@ class ShardedSlam:
         collective, the unsharded handle's bits on every rank."""
         return self.eng.search(centre, scores, **opts)
 
+    def search_scan(self, ref_scan, ref_pose=None, scan=None, centre=None, scores=False, **opts):
+        """Correlative scan-to-scan search (pfslam_search_scan): passed through like search -- nothing it reads is sharded, no
+        collective."""
+        return self.eng.search_scan(ref_scan, ref_pose, scan, centre, scores, **opts)
+
     def search_wide(self, centre=None, **opts):
         """pfslam_search's winner over a window of up to 2^31 - 1 candidates (pfslam_search_wide): passed through like search."""
         return self.eng.search_wide(centre, **opts)

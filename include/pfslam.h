@@ -30,6 +30,7 @@
  *                                      its three defects optional (see pfslam_register below)
  *   pfslam_register_batch              no counterpart: pfslam_register from many start poses in one launch, and the pick of the best run
  *   pfslam_search                      no counterpart: every pose of a window scored against a distance field of the map, the best returned
+ *   pfslam_search_scan                 no counterpart: pfslam_search's window scored against a field built from another scan's end points; no map needed
  *   pfslam_search_wide                 no counterpart: the same winner over windows of up to 2^31 - 1 candidates, by branch and bound
  *   pfslam_search_best                 no counterpart: the best candidate of each of the N best cells of such a window, by the same descent
  *   pfslam_topology_update, find_walls,
@@ -543,6 +544,45 @@ typedef struct pfslam_search_opts {
 void pfslam_search_default_opts(pfslam_search_opts *opts);
 int pfslam_search(pfslam_handle *h, const float centre[3] /* NULL = the handle's pose */, const pfslam_search_opts *opts, float pose_out[3],
                   float info[8], int32_t *scores /* NULL or one int per candidate */);
+/* pfslam_search_scan: correlative scan-to-scan search (no reference counterpart) -- "how did the robot move between these two scans".
+ * pfslam_search's window, scored against a distance field built from the END POINTS OF A REFERENCE SCAN instead of the map's nodes: the
+ * lidar-only source of the `delta` pfslam_shift_particles takes, a match before and beside the map (the handle needs NO map), and the check
+ * of a pair pfslam_check_loop_closure proposes, its two scans against each other.
+ *   ref_scan_host  n_beams ranges: the scan the field is built from
+ *   ref_pose       float[3], the pose ref_scan was taken at; NULL = (0, 0, 0)
+ *   scan_host      n_beams ranges: the scan that is searched; NULL = the handle's scan (pfslam_set_scan, the last frame's)
+ *   centre         float[3], the middle of the window; NULL = ref_pose
+ * With ref_pose = NULL, pose_out is the searched scan's pose in the reference scan's frame: the relative motion.  With ref_pose = the world
+ * pose of the previous frame, pose_out - ref_pose is the delta of pfslam_shift_particles.
+ * The candidates k, theta_a, x_i, y_j, the end points of the searched scan, the unit u and qcap, S(k) and the tie rule, pose_out,
+ * info[0..6], status 2 and the `scores` volume are pfslam_search's, word for word.  Only the field's source changes:
+ *   points       for beam b of ref_scan: (wx, wy) = CleanLidarScan(b, ref_scan[b], ref_theta), in range iff |wx| < 20 && |wy| < 20, then
+ *                P_b = (rx + wx, ry + wy): step 1 of pfslam_register at ref_pose (it honours pfslam_set_trig).  A beam out of range gives
+ *                no point.  info[7] = (float) number of points.
+ *   field        the cell (kx, ky) has q = min((int)rintf(fdiv(d2, u)), qcap), d2 = the minimum over all points of dx * dx + dy * dy with
+ *                dx = px - (float)kx * res, dy = py - (float)ky * res (pfslam_nearest's d2 with both z at 0; float, one rounding per
+ *                operation, in that order, no contraction).  A d2 too large for the conversion, infinite, or with no point at all gives
+ *                qcap.  With no point the call still succeeds: every cell is qcap, info[7] = 0, the winner follows the ordinary rule.
+ * Nothing of the handle's map, pose or particles is read.
+ * Refused (non-zero, pfslam_last_error names the cause under this function's name, outputs untouched), in this order: a NULL handle, opts,
+ * pose_out or info; a NULL ref_scan_host; a half < 0, stride outside 1 .. 64, step_theta, max_dist, reserved_ as pfslam_search; a ref_pose
+ * that is not finite; a centre that is not finite; more than 2^24 candidates; n_beams > 4096; map_res_x != map_res_y; qcap outside
+ * 1 .. 65535; more than 2^24 end points; a field above 2^26 cells (pfslam_search's bound, around the centre).
+ * Method.  k_search_ends, k_search_score and k_search_result are pfslam_search's kernels, unchanged; the field is left in the layout they
+ * read.  One thread per reference beam makes the points and counts them.  The field builder -- a function of a point list -- fills the box
+ * with qcap and then splats: a wave per point lowers the (2R + 1)^2 cells around the point's own cell, clipped to the box, to the point's q,
+ * R = ceil(max_dist / res) + 2 (a cell farther out saturates: the argument is next to the kernel); an integer minimum is exact in any
+ * order.  Sixteen-bit cells have no atomic minimum: a lane owns an aligned 32-bit word, two adjacent cells, and lowers both halves with one
+ * compare-and-swap, after a plain load that usually shows there is nothing to lower.  Its cost grows with the points and R, not with the
+ * box.  Measured: profiles/search_scan.txt.
+ * Like pfslam_search it first books the frames in flight and then runs on the handle's stream.  It writes no state another entry point
+ * reads: not the handle's scan (an uploaded scan_host goes to a buffer of its own), not the pose, not pfslam_search's results.  The field,
+ * the end points, the counts and the volume are pfslam_search's buffers (every call of either rebuilds them); the two scans, the points
+ * and the result row are its own; all belong to the handle, grow when a call needs more and go with pfslam_destroy.  One result copy and
+ * one wait per call.  Nothing is sharded, so every rank of a sharded handle gets the unsharded bits. */
+int pfslam_search_scan(pfslam_handle *h, const float *ref_scan_host, const float ref_pose[3] /* NULL = (0, 0, 0) */,
+                       const float *scan_host /* NULL = the handle's scan */, const float centre[3] /* NULL = ref_pose */,
+                       const pfslam_search_opts *opts, float pose_out[3], float info[8], int32_t *scores /* NULL or one int per candidate */);
 /* pfslam_search_wide: pfslam_search's winner over windows far beyond its cap (no reference counterpart) -- "where on this map was this scan
  * taken", at any heading: the kidnapped robot, a restart on a saved map, a loop-closure candidate checked at every heading.  +-20 m and a
  * full turn on a 40 m map at 0.025 m are 1601 x 1601 x 503 = 1 289 290 103 candidates: 77 pfslam_search calls at the cap.
