@@ -27,7 +27,7 @@ SYMBOLS = [
     "pfslam_check_loop_closure", "pfslam_get_topology", "pfslam_set_topology", "pfslam_get_closures", "pfslam_score_census", "pfslam_set_census", "pfslam_get_census_log", "pfslam_ubench_gather", "pfslam_plan_stats", "pfslam_cell_stats", "pfslam_kd_parallel_sort", "pfslam_kd_sort_threads", "pfslam_kd_whole_node",
     "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_estimate", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
     "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch", "pfslam_search", "pfslam_search_default_opts", "pfslam_search_scan", "pfslam_search_wide",
-    "pfslam_search_best", "pfslam_search_best_default_opts",
+    "pfslam_search_cov", "pfslam_search_scan_cov", "pfslam_search_cov_default_opts", "pfslam_search_best", "pfslam_search_best_default_opts",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
 
@@ -52,6 +52,11 @@ class SearchOpts(C.Structure):
     """pfslam_search_opts (include/pfslam.h)."""
     _fields_ = [("half_x", C.c_int32), ("half_y", C.c_int32), ("half_theta", C.c_int32), ("stride", C.c_int32),
                 ("step_theta", C.c_float), ("max_dist", C.c_float), ("reserved_", C.c_int32 * 2)]
+
+
+class CovOpts(C.Structure):
+    """pfslam_cov_opts (include/pfslam.h)."""
+    _fields_ = [("sigma", C.c_float), ("reserved_", C.c_int32 * 3)]
 
 
 class BestOpts(C.Structure):
@@ -172,6 +177,10 @@ def load():
     L.pfslam_search_default_opts.argtypes = [vp]
     L.pfslam_search.argtypes = [vp, vp, vp, vp, vp, vp]
     L.pfslam_search_scan.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pfslam_search_cov_default_opts.restype = None
+    L.pfslam_search_cov_default_opts.argtypes = [vp]
+    L.pfslam_search_cov.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pfslam_search_scan_cov.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pfslam_search_wide.argtypes = [vp, vp, vp, vp, vp, vp]
     L.pfslam_search_best_default_opts.restype = None
     L.pfslam_search_best_default_opts.argtypes = [vp]
@@ -682,6 +691,86 @@ class PfSlam:
         if scores:
             out["scores"] = vol
         return out
+
+    def _cov_opts(self, sigma):
+        q = CovOpts()
+        self.L.pfslam_search_cov_default_opts(C.byref(q))
+        if sigma is not None:
+            q.sigma = sigma
+        return q
+
+    @staticmethod
+    def _cov_dict(out, raw):
+        """The covariance part of search_cov()'s / search_scan_cov()'s dict from the 16 floats of cov_out."""
+        c = raw[3:9]
+        out.update({"mean": raw[0:3].copy(), "cov": np.array([[c[0], c[1], c[2]], [c[1], c[3], c[4]], [c[2], c[4], c[5]]], np.float32),
+                    "neff": float(raw[9]), "edge": float(raw[13]), "raw": raw})
+        return out
+
+    def search_cov(self, centre=None, scores=False, sigma=None, **opts):
+        """search() plus how well its winner is determined (include/pfslam.h, pfslam_search_cov): the score volume weighted with the
+        likelihood of independent Gaussian beam errors of `sigma` metres (None: pfslam_search_cov_default_opts, 0.2) and reduced as
+        estimate() reduces the cloud.  Returns search()'s dict plus mean (3), cov (3 x 3: x, y, theta), neff (the effective number of
+        candidates), edge (the share of the weight on the window's border: not small = the window cuts the distribution) and raw (the
+        16 floats of cov_out)."""
+        o = SearchOpts()
+        self.L.pfslam_search_default_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("half_x", "half_y", "half_theta", "stride", "step_theta", "max_dist"):
+                raise TypeError("search_cov() has no option %r" % k)
+            setattr(o, k, v)
+        q = self._cov_opts(sigma)
+        pose, info, raw = np.zeros(3, np.float32), np.zeros(8, np.float32), np.zeros(16, np.float32)
+        c = None if centre is None else np.ascontiguousarray(centre, dtype=np.float32).reshape(-1)
+        if c is not None and c.shape != (3,):
+            raise ValueError("search_cov(): centre must be (x, y, theta), got %d values" % c.size)
+        vol = None
+        if scores:
+            shape = tuple(2 * max(int(v), 0) + 1 for v in (o.half_theta, o.half_y, o.half_x))
+            if shape[0] * shape[1] * shape[2] <= 1 << 24:     # (a larger window is the library's to refuse)
+                vol = np.zeros(shape, np.int32)
+        _chk(self.L.pfslam_search_cov(self._h, None if c is None else _p(c), C.byref(o), C.byref(q), _p(pose), _p(info), _p(raw),
+                                      None if vol is None else _p(vol)), "pfslam_search_cov")
+        out = {"pose": pose, "status": int(info[0]), "index": int(info[1]), "beams": int(info[2]), "mean_d2": float(info[3]), "score": int(info[4]),
+               "candidates": int(info[5]), "qcap": int(info[6]), "info": info}
+        if scores:
+            out["scores"] = vol
+        return self._cov_dict(out, raw)
+
+    def search_scan_cov(self, ref_scan, ref_pose=None, scan=None, centre=None, scores=False, sigma=None, **opts):
+        """search_scan() plus how well its winner is determined (include/pfslam.h, pfslam_search_scan_cov); `sigma` and the added
+        entries mean, cov, neff, edge and raw as search_cov()'s."""
+        o = SearchOpts()
+        self.L.pfslam_search_default_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("half_x", "half_y", "half_theta", "stride", "step_theta", "max_dist"):
+                raise TypeError("search_scan_cov() has no option %r" % k)
+            setattr(o, k, v)
+        q = self._cov_opts(sigma)
+        pose, info, raw = np.zeros(3, np.float32), np.zeros(8, np.float32), np.zeros(16, np.float32)
+        ref = np.ascontiguousarray(ref_scan, dtype=np.float32).reshape(-1)
+        sc = None if scan is None else np.ascontiguousarray(scan, dtype=np.float32).reshape(-1)
+        for name, a in (("ref_scan", ref), ("scan", sc)):
+            if a is not None and len(a) != self.nb:
+                raise ValueError("search_scan_cov(): %s must hold n_beams = %d ranges, got %d" % (name, self.nb, len(a)))
+        rp = None if ref_pose is None else np.ascontiguousarray(ref_pose, dtype=np.float32).reshape(-1)
+        c = None if centre is None else np.ascontiguousarray(centre, dtype=np.float32).reshape(-1)
+        for name, a in (("ref_pose", rp), ("centre", c)):
+            if a is not None and a.shape != (3,):
+                raise ValueError("search_scan_cov(): %s must be (x, y, theta), got %d values" % (name, a.size))
+        vol = None
+        if scores:
+            shape = tuple(2 * max(int(v), 0) + 1 for v in (o.half_theta, o.half_y, o.half_x))
+            if shape[0] * shape[1] * shape[2] <= 1 << 24:     # (a larger window is the library's to refuse)
+                vol = np.zeros(shape, np.int32)
+        opt = lambda a: None if a is None else _p(a)
+        _chk(self.L.pfslam_search_scan_cov(self._h, _p(ref), opt(rp), opt(sc), opt(c), C.byref(o), C.byref(q), _p(pose), _p(info), _p(raw), opt(vol)),
+             "pfslam_search_scan_cov")
+        out = {"pose": pose, "status": int(info[0]), "index": int(info[1]), "beams": int(info[2]), "mean_d2": float(info[3]), "score": int(info[4]),
+               "candidates": int(info[5]), "qcap": int(info[6]), "points": int(info[7]), "info": info}
+        if scores:
+            out["scores"] = vol
+        return self._cov_dict(out, raw)
 
     def search_wide(self, centre=None, **opts):
         """pfslam_search's winner over windows of up to 2^31 - 1 candidates, found by branch and bound (include/pfslam.h,

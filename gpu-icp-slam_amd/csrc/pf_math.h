@@ -299,6 +299,27 @@ PF_HD float asinf_spec(float x)
 // rsqrt(float) as the CUDA host headers give it to svd3.h
 PF_HD float rsqrtf_spec(float x) { return (float)(1.0 / sqrt((double)x)); }
 
+// 2^-t for t >= 0 (pfslam_search_cov's weights; the specification is in include/pfslam.h): 0 from t = 64 on (and for a NaN), else with
+// n = (int)t and f = t - n in [0, 1) the Taylor polynomial of 2^-f to degree 16 in double -- Horner, a multiply and an add per step, two
+// roundings, never an fma -- scaled by 2^-n (exact) and rounded once to float.  p is within 4.5e-16 relative of 2^-f; exp2m(0) == 1.
+PF_HD float exp2m(float t)
+{
+    // C_k = (-ln 2)^k / k!
+    const double C[17] = {0x1p+0, -0x1.62e42fefa39efp-1, 0x1.ebfbdff82c58ep-3, -0x1.c6b08d704a0bfp-5, 0x1.3b2ab6fba4e77p-7,
+                          -0x1.5d87fe78a6730p-10, 0x1.430912f86c786p-13, -0x1.ffcbfc588b0c5p-17, 0x1.62c0223a5c822p-20,
+                          -0x1.b5253d395e7c1p-24, 0x1.e4cf5158b8ec7p-28, -0x1.e8cac7351bb22p-32, 0x1.c3bd650fc2983p-36,
+                          -0x1.816193166d0f7p-40, 0x1.314964d5878a7p-44, -0x1.c36e843b0401ep-49, 0x1.38e89ae79f8b1p-53};
+    if (!(t < 64.0f)) return 0.0f;
+    const int n = (int)t;
+    const double f = (double)t - (double)n;
+    double p = C[16];
+#pragma unroll
+    for (int k = 15; k >= 0; k--) p = p * f + C[k];
+    union { double d; uint64_t u; } s;
+    s.u = (uint64_t)(1023 - n) << 52; // 2^-n, n in 0 .. 63
+    return (float)(p * s.d);
+}
+
 // ---- RNG: utilhash / makeSeededRandomEngine (kernel.cu:89-102) + thrust::minstd_rand ----
 PF_HD uint32_t utilhash(uint32_t a)
 {

@@ -177,6 +177,11 @@ struct pfslam_handle {
     float *scan_in = nullptr;
     float2 *scan_pts = nullptr;
     unsigned long long *scan_state = nullptr;
+    // pfslam_search_cov's / pfslam_search_scan_cov's own buffers (everything else is pfslam_search's and pfslam_search_scan's above): 12 tile
+    // sums per 4096-candidate tile of the volume, growing with the window, and key + box words + result row + point count + cov_out
+    float *cov_part = nullptr;
+    size_t cov_part_cap = 0;
+    unsigned long long *cov_state = nullptr;
     float *est_part = nullptr; // pfslam_estimate: 11 tile sums per 4096-particle tile of the GLOBAL cloud, then the 16 output floats
     // grid path
     int8_t *grid = nullptr;
@@ -1062,7 +1067,7 @@ extern "C" int pfslam_destroy(pfslam_handle *h)
                     h->fit, h->fit_i, h->partial, h->mkey, h->order2, h->cells, h->stats, h->pose, h->start, h->icp_tar, h->icp_cor, h->icp_dbg,
                     h->free_mask, h->blk_cnt, h->wall_cell, h->free_cell, h->wall_pts, h->free_pts,
                     h->wall_c, h->free_c, h->counts, h->tile_r, h->tile_r2, h->sums, h->cdf,
-                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->srch_field, h->srch_ends, h->srch_nin, h->srch_scores, h->srch_state, h->wide_field, h->wide_ends, h->wide_nin, h->wide_nodes, h->wide_lb, h->wide_state, h->best_tab, h->best_list, h->best_state, h->scan_in, h->scan_pts, h->scan_state, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
+                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->srch_field, h->srch_ends, h->srch_nin, h->srch_scores, h->srch_state, h->wide_field, h->wide_ends, h->wide_nin, h->wide_nodes, h->wide_lb, h->wide_state, h->best_tab, h->best_list, h->best_state, h->scan_in, h->scan_pts, h->scan_state, h->cov_part, h->cov_state, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (h->own_global) {
@@ -2472,5 +2477,6 @@ static int frame_v2_finish(pfslam_handle *h);
 #include "pfslam_register_batch.hip.inc"
 #include "pfslam_search.hip.inc"
 #include "pfslam_search_scan.hip.inc"
+#include "pfslam_search_cov.hip.inc"
 #include "pfslam_search_wide.hip.inc"
 #include "pfslam_search_best.hip.inc"

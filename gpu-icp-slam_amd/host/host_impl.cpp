@@ -332,6 +332,44 @@ bool pfslamSearchScan(const float *ref_scan, glm::vec3 ref_pose, glm::vec3 &pose
     if (index) *index = (int)info[1];
     return true;
 }
+bool pfslamSearchCov(glm::vec3 centre, float sigma, glm::vec3 &pose, float cov[16], int *index)
+{
+    if (!g_handle || !cov) return false;
+    pfslam_search_opts o;
+    pfslam_search_default_opts(&o);
+    pfslam_cov_opts q;
+    pfslam_search_cov_default_opts(&q);
+    q.sigma = sigma;
+    const float c[3] = {centre.x, centre.y, centre.z};
+    float p[3], info[8], cv[16];
+    if (pfslam_search_cov(g_handle, c, &o, &q, p, info, cv, nullptr)) {
+        fprintf(stderr, "pfslamSearchCov: %s\n", pfslam_last_error());
+        return false;
+    }
+    pose = glm::vec3(p[0], p[1], p[2]);
+    memcpy(cov, cv, sizeof(cv));
+    if (index) *index = (int)info[1];
+    return true;
+}
+bool pfslamSearchScanCov(const float *ref_scan, glm::vec3 ref_pose, float sigma, glm::vec3 &pose, float cov[16], int *index, const float *scan)
+{
+    if (!g_handle || !cov) return false;
+    pfslam_search_opts o;
+    pfslam_search_default_opts(&o);
+    pfslam_cov_opts q;
+    pfslam_search_cov_default_opts(&q);
+    q.sigma = sigma;
+    const float r[3] = {ref_pose.x, ref_pose.y, ref_pose.z};
+    float p[3], info[8], cv[16];
+    if (pfslam_search_scan_cov(g_handle, ref_scan, r, scan, nullptr, &o, &q, p, info, cv, nullptr)) {
+        fprintf(stderr, "pfslamSearchScanCov: %s\n", pfslam_last_error());
+        return false;
+    }
+    pose = glm::vec3(p[0], p[1], p[2]);
+    memcpy(cov, cv, sizeof(cv));
+    if (index) *index = (int)info[1];
+    return true;
+}
 void pfslamShiftParticles(glm::vec3 delta)
 {
     if (!g_handle) return;

@@ -86,6 +86,13 @@ bool pfslamSearch(glm::vec3 centre, glm::vec3 &pose, int *index);
 // Reads the filter, changes nothing in it; like getPCData it first waits for the frames in flight.  index may be null.  false (and a line
 // on stderr): no live filter or a null ref_scan; the outputs are then untouched.
 bool pfslamSearchScan(const float *ref_scan, glm::vec3 ref_pose, glm::vec3 &pose, int *index, const float *scan = nullptr);
+// pfslamSearch / pfslamSearchScan and how well their winner is determined (include/pfslam.h, pfslam_search_cov and pfslam_search_scan_cov):
+// the same call and the same pose and *index, and on top cov[16] = the weighted mean pose [0..2], the covariance xx, xy, xtheta, yy, ytheta,
+// thetatheta [3..8], the effective number of candidates [9] and the share of the weight on the window's border [13] of the score volume,
+// weighted with the likelihood of independent Gaussian beam errors of `sigma` metres (the library's default: 0.2).  false as above, and
+// for a sigma that is not finite or not > 0; the outputs are then untouched.
+bool pfslamSearchCov(glm::vec3 centre, float sigma, glm::vec3 &pose, float cov[16], int *index);
+bool pfslamSearchScanCov(const float *ref_scan, glm::vec3 ref_pose, float sigma, glm::vec3 &pose, float cov[16], int *index, const float *scan = nullptr);
 // The odometry hook (include/pfslam.h, pfslam_shift_particles): every particle and the robot's pose += delta.
 void pfslamShiftParticles(glm::vec3 delta);
 // The same winner over a window too large to score candidate by candidate (include/pfslam.h, pfslam_search_wide): +-half_metres in x and

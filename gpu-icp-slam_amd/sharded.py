@@ -184,6 +184,14 @@ class ShardedSlam:
         collective."""
         return self.eng.search_scan(ref_scan, ref_pose, scan, centre, scores, **opts)
 
+    def search_cov(self, centre=None, scores=False, sigma=None, **opts):
+        """search plus the mean, covariance and Neff of its score volume (pfslam_search_cov): passed through like search."""
+        return self.eng.search_cov(centre, scores, sigma, **opts)
+
+    def search_scan_cov(self, ref_scan, ref_pose=None, scan=None, centre=None, scores=False, sigma=None, **opts):
+        """search_scan plus the mean, covariance and Neff of its score volume (pfslam_search_scan_cov): passed through like search_scan."""
+        return self.eng.search_scan_cov(ref_scan, ref_pose, scan, centre, scores, sigma, **opts)
+
     def search_wide(self, centre=None, **opts):
         """pfslam_search's winner over a window of up to 2^31 - 1 candidates (pfslam_search_wide): passed through like search."""
         return self.eng.search_wide(centre, **opts)

@@ -31,6 +31,7 @@
  *   pfslam_register_batch              no counterpart: pfslam_register from many start poses in one launch, and the pick of the best run
  *   pfslam_search                      no counterpart: every pose of a window scored against a distance field of the map, the best returned
  *   pfslam_search_scan                 no counterpart: pfslam_search's window scored against a field built from another scan's end points; no map needed
+ *   pfslam_search_cov, _scan_cov       no counterpart: either search, plus the weighted mean pose, 3x3 covariance and Neff of its score volume
  *   pfslam_search_wide                 no counterpart: the same winner over windows of up to 2^31 - 1 candidates, by branch and bound
  *   pfslam_search_best                 no counterpart: the best candidate of each of the N best cells of such a window, by the same descent
  *   pfslam_topology_update, find_walls,
@@ -583,6 +584,84 @@ int pfslam_search(pfslam_handle *h, const float centre[3] /* NULL = the handle's
 int pfslam_search_scan(pfslam_handle *h, const float *ref_scan_host, const float ref_pose[3] /* NULL = (0, 0, 0) */,
                        const float *scan_host /* NULL = the handle's scan */, const float centre[3] /* NULL = ref_pose */,
                        const pfslam_search_opts *opts, float pose_out[3], float info[8], int32_t *scores /* NULL or one int per candidate */);
+/* pfslam_search_cov / pfslam_search_scan_cov: pfslam_search / pfslam_search_scan, and how well the winner is determined (no reference
+ * counterpart).  A winner alone says nothing about its uncertainty: in a corridor it is arbitrary along the corridor.  The score volume is
+ * up to 2^24 poses that lack only weights; these calls give it weights and run pfslam_estimate's reduction over it: the information a
+ * pose-graph constraint needs, the trust a filter puts into the match, the spread of the `delta` pfslam_shift_particles takes.
+ * Definition by reference.  pose_out, info and scores are bit for bit what pfslam_search / pfslam_search_scan return for the same
+ * arguments, status 2 and info[7] (the point count of the scan form) included; the candidates k, theta_a, x_i, y_j and S(k) are theirs,
+ * word for word.  Only cov_out is new.  All arithmetic is float, one rounding per operation, in the order written, no contraction,
+ * divisions (fdiv) correctly rounded, except where stated.
+ *   scale     hs = fdiv(u * 1.442695f, (2.0f * sigma) * sigma)     (the constant has the float bits 0x3fb8aa3b; u is the search's unit)
+ *             The model: independent Gaussian beam errors, likelihood proportional to exp(-S u / (2 sigma^2)).
+ *   weights   Smin = the winner's S.  A candidate of a heading that takes no part has w_k = 0; every other one
+ *             t_k = (float)(S_k - Smin) * hs     (the difference is an exact int32; the conversion rounds to nearest even above 2^24)
+ *             w_k = exp2m(t_k)
+ *   exp2m(t), t >= 0:  0.0f if !(t < 64.0f); else n = (int)t, f = (double)t - (double)n (exact, in [0, 1)), in double p = C16, then for
+ *             k = 15 down to 0  p = p * f + C_k  (a multiply, then an add: two roundings, never an fma), w = (float)(p * 2^-n) (the
+ *             scaling is exact: one rounding to float).  C_k = (-ln 2)^k / k! as these doubles:
+ *               C0  0x1p+0                    C1  -0x1.62e42fefa39efp-1     C2  0x1.ebfbdff82c58ep-3      C3  -0x1.c6b08d704a0bfp-5
+ *               C4  0x1.3b2ab6fba4e77p-7      C5  -0x1.5d87fe78a6730p-10    C6  0x1.430912f86c786p-13     C7  -0x1.ffcbfc588b0c5p-17
+ *               C8  0x1.62c0223a5c822p-20     C9  -0x1.b5253d395e7c1p-24    C10 0x1.e4cf5158b8ec7p-28     C11 -0x1.e8cac7351bb22p-32
+ *               C12 0x1.c3bd650fc2983p-36     C13 -0x1.816193166d0f7p-40    C14 0x1.314964d5878a7p-44     C15 -0x1.c36e843b0401ep-49
+ *               C16 0x1.38e89ae79f8b1p-53
+ *             p is within 4.5e-16 relative of 2^-f (measured over 200 000 arguments); w(0) = 1 exactly, so S0 >= 1 whenever a heading takes
+ *             part; the cut at t >= 64 loses nothing a float sum of 2^24 terms next to a 1 can hold.  (pf::exp2m in csrc/pf_math.h.)
+ *   moments   pfslam_estimate's, word for word: particle i becomes candidate k, its pose (x_i, y_j, theta_a) of k, gn the number of
+ *             candidates, csum the canonical sum over k ascending with tiles of 4096 consecutive k (2^24 candidates are exactly the
+ *             4096 x 4096 a csum can hold).
+ *   cov_out   [0..2] mean m   [3..8] C: xx, xy, xtheta, yy, ytheta, thetatheta   [9] Neff = (S0 * S0) / S2   [10] S0   [11] S2
+ *             [12] (float)candidates   [13] border share = fdiv(csum(e_k ? w_k : 0), S0)   [14] hs   [15] 0
+ *             e_k: k lies on the first or the last index of a dimension that has more than one candidate.  A border share that is not
+ *             small says the window cuts the distribution; C is then a lower bound.
+ *             With status 2 the call succeeds and cov_out is all zero except [12] and [14].
+ * Remarks.  The heading mean is linear, as in pfslam_estimate: headings are not wrapped.  Neff near 1 means the posterior is narrower
+ * than the lattice; the caller then adds the quantisation variance (stride res)^2 / 12 per axis (step_theta^2 / 12 for the heading).  The
+ * beams of a scan are not independent: a caller who wants n_ind effective beams out of n_in passes sigma_beam * sqrt(n_in / n_ind); the
+ * default 0.2 is such a tempered value (at sigma = 0.05 the posteriors of the two scenarios below are narrower than the lattice, Neff 1.0
+ * to 2.3).  The products w d d can reach float denormals and are kept: nothing is flushed, on the device or in the restatement.
+ *   Measured with the restatement (tests/test_search_cov_spec.py), scan to scan, 1081 beams, window 21 x 21 x 9 at stride 1, the searched
+ *   scan cast 0.1 m / 0.05 m / 0.0125 rad from the reference scan and the window centred there, sigma 0.2: between two walls y = +-1 from x = -30 to 30 the winner is
+ *   0.1 m off along the corridor with nothing to show for it, and the covariance says so: sd_x 0.106 m, sd_y 0.0030 m, sd_theta
+ *   0.00037 rad, Neff 11.9, border share 0.040.  In a closed 6 m x 4 m room the winner is the pose: sd 0.014 m / 0.0049 m / 0.0050 rad,
+ *   Neff 2.9, border share 2e-17.
+ * Refused (non-zero, pfslam_last_error names the cause under the new function's name, outputs untouched): everything pfslam_search (or
+ * pfslam_search_scan) refuses, in its order and wording, a NULL cov or cov_out joining the first check; behind those and before any
+ * launch: sigma not finite or not > 0; a reserved_ of pfslam_cov_opts that is not 0; hs not finite or not > 0.
+ * Method.  k_search_ends, k_search_field / the scan splat, k_search_score and k_search_result run unchanged; the volume is always built
+ * on the device and copied only when `scores` is not NULL.  The reduction is pfslam_estimate's three passes ordered by the stream --
+ * moments, centred moments with the means re-derived per workgroup from the tile sums, the final sums -- one workgroup per tile of 4096
+ * consecutive k, staged into LDS as float [4][4096] = (w, x, y, theta): one coalesced load of S_k per candidate, w_k from exp2m (recomputed
+ * in the second pass, not stored: the same function of the same bits), the pose from k, which a thread divides into (a, j, i) once and
+ * then steps.  The border sum is a twelfth quantity, summed by the wave that is idle in the moment pass.  Up to one tile one workgroup
+ * does all three passes.  The summation order is the device functions' of pfslam_estimate, reused as they are.
+ *   Measured on one MI355X, 1081 beams, the benchmark's 100 000-point map (profiles/search_cov.txt; HIP events around whole calls, beside
+ *   pfslam_search with scores = NULL in the same process): the default window of 55 473 candidates 1.10 ms against 1.06 ms; 549 153
+ *   candidates 1.38 ms against 1.34 ms; 16 776 177 candidates, just under the cap, 10.9 ms against 10.0 ms (on the 4000-point map 1.77 /
+ *   1.73 ms, 2.15 / 2.11 ms, 11.8 / 10.9 ms); pfslam_search_scan_cov's default call without a map 0.22 ms against 0.18 ms.  The three
+ *   reduction launches alone, from a kernel trace: 34 us for the default window (14 tiles), 40 us for 135 tiles, 0.87 ms for 4096
+ *   tiles -- moments 139 us, centred moments 587 us, final sums 147 us; 450 us of the second pass are the means re-derived by every
+ *   wave of every workgroup from 4 x 4096 tile sums, as pfslam_estimate's kernel does.
+ *   Kernel resources (VGPRs / LDS bytes per workgroup / waves per SIMD): moments 18 / 65 536 / 3, centred moments 19 / 65 536 / 3, final
+ *   sums 33 / 0 / 8, the one-workgroup form 31 / 65 536 / 3 (pfslam_estimate's: 23, 23, 32, 28): LDS is the only limit.
+ * Like pfslam_search the call first books the frames in flight, runs on the handle's stream and honours pfslam_set_trig; one result copy
+ * (cov_out rides with the result row) and one wait (+ one for a NULL centre of pfslam_search_cov).  The field, end points, counts and
+ * volume are pfslam_search's buffers, the scans and points pfslam_search_scan's; the tile sums and the result row are buffers of its own
+ * that belong to the handle, grow when a call needs more and go with pfslam_destroy.  No state another entry point reads is written.
+ * Nothing is sharded, so every rank of a sharded handle gets the unsharded bits. */
+typedef struct pfslam_cov_opts {
+    float   sigma;         /* metres; finite, > 0 */
+    int32_t reserved_[3];  /* must be 0 */
+} pfslam_cov_opts;
+/* {0.2f, {0, 0, 0}} */
+void pfslam_search_cov_default_opts(pfslam_cov_opts *o);
+int pfslam_search_cov(pfslam_handle *h, const float centre[3] /* NULL = the handle's pose */, const pfslam_search_opts *opts,
+                      const pfslam_cov_opts *cov, float pose_out[3], float info[8], float cov_out[16],
+                      int32_t *scores /* NULL or one int per candidate */);
+int pfslam_search_scan_cov(pfslam_handle *h, const float *ref_scan_host, const float ref_pose[3] /* NULL = (0, 0, 0) */,
+                           const float *scan_host /* NULL = the handle's scan */, const float centre[3] /* NULL = ref_pose */,
+                           const pfslam_search_opts *opts, const pfslam_cov_opts *cov, float pose_out[3], float info[8], float cov_out[16],
+                           int32_t *scores /* NULL or one int per candidate */);
 /* pfslam_search_wide: pfslam_search's winner over windows far beyond its cap (no reference counterpart) -- "where on this map was this scan
  * taken", at any heading: the kidnapped robot, a restart on a saved map, a loop-closure candidate checked at every heading.  +-20 m and a
  * full turn on a 40 m map at 0.025 m are 1601 x 1601 x 503 = 1 289 290 103 candidates: 77 pfslam_search calls at the cap.
