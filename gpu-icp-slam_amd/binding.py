@@ -913,9 +913,9 @@ class PfSlam:
 
     def debug_math(self, which, x):
         x = np.ascontiguousarray(x, dtype=np.float32).ravel()
-        out = np.empty(len(x) * (2 if which in (0, 6, 7) else 1), np.float32)
+        out = np.empty(len(x) * (2 if which in (0, 6, 7, 8) else 1), np.float32)
         _chk(self.L.pfslam_debug_math(self._h, which, _p(x), len(x), _p(out)), "pfslam_debug_math")
-        if which == 6:
+        if which in (6, 8):
             return out.view(np.int32).reshape(-1, 2)
         return out.reshape(-1, 2) if which in (0, 7) else out
 

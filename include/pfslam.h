@@ -72,7 +72,10 @@ typedef struct pfslam_config {
                                      * only well defined on a square grid; pfslam_create refuses anything else.  The rays' cells
                                      * come from a closed form of the reference's Bresenham walk whose product k * deltay is 32-bit:
                                      * it is exact while a ray is shorter than 46 341 cells, that is while 20 m / res stays below
-                                     * that (res above about 0.43 mm) */
+                                     * that (res above about 0.43 mm).  Oblong cells (map_res_x != map_res_y) are supported by
+                                     * every frame and stage call, bit for bit like square ones, the persistent lattice-cell rows
+                                     * included (tests/test_gpu_oblong_cells.py); the pfslam_search* entry points refuse them where
+                                     * their comments below say so */
     int32_t kd_capacity;   /* KD_MAX_SIZE (kernel.cu:77); nodes, at most 2^27 - 1.  A frame whose new walls do not fit inserts
                             * none of them and fails ("kd_capacity exhausted"; reported by the call that books the frame, see
                             * pfslam_step) -- the reference has no bound check at all */

@@ -184,9 +184,11 @@ def icp(tree, robot, start, scan):
 
 
 def get_walls(scan, cx, cy, theta, dimx=1600, dimy=1600, res=0.025):
+    """res: one cell size for both axes, or (res_x, res_y)."""
     scan = np.ascontiguousarray(scan, dtype=np.float32)
     fm = np.zeros(dimx * dimy, np.uint8); wm = np.zeros(dimx * dimy, np.uint8)
-    lib().orc_get_walls(P(scan), len(scan), cx, cy, float(theta), P(fm), P(wm), dimx, dimy, res, res)
+    rx, ry = res if isinstance(res, (tuple, list)) else (res, res)
+    lib().orc_get_walls(P(scan), len(scan), cx, cy, float(theta), P(fm), P(wm), dimx, dimy, rx, ry)
     return fm, wm
 
 
@@ -208,17 +210,17 @@ class Topology(C.Structure):
     def nodes(self):
         return np.array([[self.pos[k][0], self.pos[k][1], self.dist[k]] for k in range(self.n_nodes)], np.float32)
 
-    def loop_closure(self, grid, robot, cap=4096):
+    def loop_closure(self, grid, robot, cap=4096, patch=None):
         r = np.ascontiguousarray(robot, np.float32)
         pairs = np.zeros((cap, 2), np.int32)
-        patch = default_patch()
+        patch = patch if patch is not None else default_patch()
         n = lib().orc_check_loop_closure(C.byref(self), P(grid), grid.shape[0], grid.shape[1], C.byref(patch), P(r), P(pairs), cap)
         return pairs[:min(n, cap)].copy()
 
 
-def find_walls(grid, a, b):
+def find_walls(grid, a, b, patch=None):
     a = np.ascontiguousarray(a, np.float32); b = np.ascontiguousarray(b, np.float32)
-    patch = default_patch()
+    patch = patch if patch is not None else default_patch()
     return lib().orc_find_walls(P(grid), grid.shape[0], grid.shape[1], C.byref(patch), P(a), P(b))
 
 
