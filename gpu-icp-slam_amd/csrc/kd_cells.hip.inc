@@ -54,7 +54,7 @@
 //   appends to the list while k_cells_update<true> runs, and an entry whose slot is counted but not yet written must not be read
 //   [4] [5] capacity of the list and of the pool in use (<= PF_CELL_LIST_CAP / PF_CELL_POOL_CAP: the allocations; smaller in tests of the
 //   overflow paths, PFSLAM_CELL_LIST_CAP / PFSLAM_CELL_POOL_CAP)  [128] [129] lattice index (in sub-cells) of the window's corner  [6] flags (PF_CF_*)  [8] live rows  [9] sum n1  [10] sum n2 (without
-//   the 15s)  [11] sub-cells without a row  [12 .. 15] since the wipe: cells walked from the root / extensions / looks that found a
+//   the 15s)  [11] sub-cells without a row (too many candidates, pool exhausted, or the four of a cell the full list refused)  [12 .. 15] since the wipe: cells walked from the root / extensions / looks that found a
 //   cell unchanged / cells claimed (the last three grow with every pass)
 enum { PF_CS_COUNT = 0, PF_CS_POOL, PF_CS_SNAP, PF_CS_PAD3, PF_CS_LIST_CAP, PF_CS_POOL_CAP, PF_CS_FLAGS, PF_CS_PAD, PF_CS_ROWS, PF_CS_N1, PF_CS_N2,
        PF_CS_NONE, PF_CS_CUR_FRESH, PF_CS_CUR_EXT, PF_CS_CUR_REUSED, PF_CS_CUR_CLAIMED, PF_CS_WORDS = 32,
@@ -251,6 +251,7 @@ __global__ __launch_bounds__(PF_MARK_THREADS) void k_cells_mark(const pf::KdGrou
                 else { // list full: the cell gets no row until the next wipe
                     atomicExch(&tab[idx], PF_CELL_FALLBACK);
                     atomicOr(&cs[PF_CS_FLAGS], PF_CF_LIST_FULL);
+                    atomicAdd(&cs[PF_CS_NONE], PF_CELL_SUB * PF_CELL_SUB); // its sub-cells go without rows (no record: nobody unbooks them)
                 }
             }
         }
@@ -269,6 +270,7 @@ __global__ __launch_bounds__(PF_MARK_THREADS) void k_cells_mark(const pf::KdGrou
             else {
                 atomicExch(&tab[s_claim[k]], PF_CELL_FALLBACK);
                 atomicOr(&cs[PF_CS_FLAGS], PF_CF_LIST_FULL);
+                atomicAdd(&cs[PF_CS_NONE], PF_CELL_SUB * PF_CELL_SUB);
             }
         }
     };

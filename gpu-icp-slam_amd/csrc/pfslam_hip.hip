@@ -272,7 +272,8 @@ struct pfslam_handle {
     // shift, replaced by the device's own maximum + 1 whenever a frame's header comes in
     float theta_bound = 0.0f, theta_shift = 0.0f;
     int theta_shift_seq = 0;
-    bool cells_suspended = false;  // the list / pool overflowed twice in a row: round-2 plan until the next upload_tree
+    bool cells_suspended = false;  // the list / pool overflowed in two booked frames whose frame NUMBERS (the caller's) differ and lie at most 16
+                                   // apart -- a lower number counts too (consume_frame): round-2 plan until the next upload_tree
     int cells_full_frame = -1;
     bool balance_external = false; // multi-GPU: ONE rank of the node re-balances, the others adopt its arrays (pfslam_set_shard_balance)
     int cells_wipe_seq = 0;       // header flags of frames with an older ticket predate the last wipe
@@ -2085,11 +2086,12 @@ extern "C" int pfslam_plan_stats(pfslam_handle *h, double out[10])
 
 // the persistent lattice-cell rows: out[0] cells claimed since the last wipe (one record each), [1] live rows (one per sub-cell: up to four
 // per cell), [2] mean first-descent candidates per row, [3] mean re-descent candidates per row, [4] sub-cells without a row (too many
-// candidates / pool exhausted: generic lanes), [5] 16-byte pool slots used, [6] [7] lattice index of the window's corner cell,
+// candidates / pool exhausted / their cell refused by a full list: generic lanes), [5] 16-byte pool slots used, [6] [7] lattice index of the window's corner cell,
 // [8 .. 11] since the last wipe: cells walked from the root / extensions (a link of the cell had gained a node) / looks that found a
 // cell unchanged (reused as it was) / cells claimed by the marking passes, [12] device flags (PF_CF_*: 1 list full, 2 pool full,
 // 8 cloud far from the window centre), [13] publishing updates since the last wipe (the divisor of [9] [10]), [14] wipes so far,
-// [15] 1 = suspended (list / pool overflowed twice in a row: the round-2 plan scores until the map is replaced or re-balanced).
+// [15] 1 = suspended (list / pool overflowed in two frames whose frame numbers differ, the later-booked one at most 16 above the other:
+// the round-2 plan scores until the map is replaced or re-balanced).  [6] [7] are in SUB-cells (PF_CELL_SUB per lattice cell).
 // [0 .. 13] are zero when the last scoring pass did not use cell rows.
 extern "C" int pfslam_cell_stats(pfslam_handle *h, double out[16])
 {

@@ -2016,8 +2016,10 @@ static int consume_frame(pfslam_handle *h)
         if ((hdr->flags & (PF_HDR_CELLS_WIPE | PF_HDR_CELLS_FULL)) && f.seq >= h->cells_wipe_seq) {
             h->cells_wipe_pending = true; // before the next scoring pass
             // The list / pool fills when the cloud is so wide that its beam ends cover more lattice cells than there are records (a
-            // 1 m cloud: millions): wiping every few frames would rebuild the same overfull table over and over.  Twice within 16
-            // frames: the scan-match kernel goes back to the round-2 plan until the map is replaced or re-balanced (upload_tree).
+            // 1 m cloud: millions): wiping every few frames would rebuild the same overfull table over and over.  A second overflow
+            // whose frame NUMBER -- the caller's, not a count of frames -- differs from the first one's and is at most 16 above it (a
+            // lower or far lower number passes this test too): the scan-match kernel goes back to the round-2 plan until the map is
+            // replaced or re-balanced (upload_tree).  Numbers more than 16 apart never suspend, however many frames overflow.
             if (hdr->flags & PF_HDR_CELLS_FULL) {
                 if (h->cells_full_frame >= 0 && f.frame - h->cells_full_frame <= 16 && f.frame != h->cells_full_frame) h->cells_suspended = true;
                 h->cells_full_frame = f.frame;

@@ -323,11 +323,13 @@ int pfslam_ubench_gather(pfslam_handle *h, double out[4]);
 int pfslam_plan_stats(pfslam_handle *h, double out[10]);
 /* the persistent lattice-cell rows (csrc/kd_cells.hip.inc): out[0] lattice cells claimed since the last wipe, [1] live rows (one per
  * sub-cell: up to four per cell), [2] mean first-descent candidates per row, [3] mean re-descent candidates per row, [4] sub-cells
- * without a row, [5] 16-byte pool slots used, [6] [7] lattice index of the window's corner cell, [8 .. 11] since the last wipe:
+ * without a row (too many candidates, the pool exhausted, or the four of a cell that a full list refused), [5] 16-byte pool slots used, [6] [7] index of the window's corner in sub-cells (two per lattice cell and axis), [8 .. 11] since the last wipe:
  * cells walked from the root / extensions (one of the cell's links had gained a node) / looks that found a cell unchanged / cells
  * claimed, [12] device flags (1 list full, 2 pool full, 8 cloud far from the window centre), [13] publishing updates since the
  * last wipe (divide [9] and [10] by it for per-frame figures), [14] wipes so far, [15] 1 = suspended: the list / pool overflowed
- * twice within 16 frames (a cloud too wide for the table), the round-2 plan scores until the map is replaced or re-balanced.
+ * in two frames whose frame numbers -- the `frame` arguments of pfslam_step / pfslam_shard_disperse, not a count of calls -- differ,
+ * the second one's at most 16 above the first one's (a lower number counts as well; numbers more than 16 apart never suspend): a
+ * cloud too wide for the table, the round-2 plan scores until the map is replaced or re-balanced.
  * [0 .. 13] are zero when the last scoring pass did not use cell rows. */
 int pfslam_cell_stats(pfslam_handle *h, double out[16]);
 /* mean duration (ms) of the 2-D scan-match kernel alone and of the whole 2-D scoring pass (kernel + partial sums + min / max / argmax +

@@ -25,10 +25,20 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 t_end = time.time() + budget
 cases = frames_total = refused = 0
+wipes_total = suspended_total = 0   # the lattice-cell rows' recovery paths, summed over the handles (cell_stats just before close)
 
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.int32)
+
+
+def tally_cells(h):
+    global wipes_total, suspended_total
+    try:
+        st = h.cell_stats()
+    except pkg.PfSlamError:   # (a handle whose last frame was refused says so again)
+        return
+    wipes_total += int(st["wipes"]); suspended_total += int(st["suspended"])
 
 
 def mutate(scan, rng):
@@ -114,6 +124,7 @@ while time.time() < t_end:
             print("DIVERGED", desc, "frame", f, tg, to, h.pose, o.pose); sys.exit(1)
         frames_total += 1
     if not ok:
+        tally_cells(h)
         h.close(); o.close()
         refused += 1
         continue
@@ -127,6 +138,8 @@ while time.time() < t_end:
     for fld in ("x", "y", "theta", "w"):
         if not (bits(got[fld]) == bits(want[fld])).all():
             print("DIVERGED particles", fld, desc); sys.exit(1)
+    tally_cells(h)
     h.close(); o.close()
     cases += 1
-print("fuzz ok%s: %d cases, %d frames (%d cases ended by a loud kd_capacity refusal)" % (" (device library, against the stage shadow)" if DEVLIB else "", cases, frames_total, refused))
+print("fuzz ok%s: %d cases, %d frames (%d cases ended by a loud kd_capacity refusal); cell rows: %d wipes, %d handles ended suspended" %
+      (" (device library, against the stage shadow)" if DEVLIB else "", cases, frames_total, refused, wipes_total, suspended_total))

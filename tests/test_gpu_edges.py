@@ -273,3 +273,7 @@ def test_differential_fuzz_of_the_frame_loop():
         env = dict(os.environ, PFSLAM_PLAN_MIN_N="1", **extra)
         out = subprocess.run([sys.executable, os.path.join(root, "tests", "fuzz_step.py"), "15", seed], capture_output=True, text=True, timeout=300, env=env)
         assert out.returncode == 0 and "fuzz ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+        if "PFSLAM_CELL_LIST_CAP" in extra:   # ... and were reached: rows wiped, handles that ended suspended
+            import re
+            m = re.search(r"cell rows: (\d+) wipes, (\d+) handles ended suspended", out.stdout)
+            assert m and int(m.group(1)) > 0 and int(m.group(2)) > 0, out.stdout[-2000:]
