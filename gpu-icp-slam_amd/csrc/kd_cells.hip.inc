@@ -1070,19 +1070,24 @@ __device__ __forceinline__ bool cell_visit(const uint4 cd, float wx, float wy, f
 // (Parking the ~9 % of queries that do look at re-descent candidates in their lane and resolving them a few beams later, many
 // lanes at once, was measured: same kernel time -- the generic tail runs in 15 % of the (wave, beam) rows, not in most.)
 #define PF_ROW_SLACK 4 /* pool slots behind the last row that a four-slot request may touch */
-template <bool CENSUS = false, int GUARD = 1>
+template <bool CENSUS = false, int GUARD = 1, bool ENDS = false>
 __global__ __launch_bounds__(64) void k_score_kd_cells(const float *__restrict__ px, const float *__restrict__ py,
                                                        const float *__restrict__ pth, int n, const float *__restrict__ scan,
                                                        const pf::BeamParts *__restrict__ beams, int nb, int beams_per_chunk, pf::KdView tree,
                                                        CellGeom geo, const unsigned *__restrict__ tab, const uint4 *__restrict__ pool,
                                                        const int *__restrict__ cs, const int *__restrict__ order, int direct,
                                                        float *__restrict__ out, int out_mode, pf::KdCensus *__restrict__ census = nullptr,
-                                                       unsigned long long *__restrict__ probe = nullptr, const double2 *__restrict__ tparts = nullptr)
+                                                       unsigned long long *__restrict__ probe = nullptr, const double2 *__restrict__ tparts = nullptr,
+                                                       const int *__restrict__ starts = nullptr, unsigned long long *__restrict__ probe_ends = nullptr)
 {
     pf_stamp(probe);
+    // (frame probe: when the last-indexed wave starts -- with groups fastest and the shortest chunks last, the launch's tail begins here)
+    if (probe && blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1 && threadIdx.x == 0) probe[PB_SCORE_LAST - PB_SCORE] = wall_clock64();
     const int g = blockIdx.x, slot = g * 64 + threadIdx.x;
-    const int j0 = blockIdx.y * beams_per_chunk;
-    const int j1 = min(nb, j0 + beams_per_chunk);
+    // this wave's beams: chunk blockIdx.y of the plan (score_plan.h: the round-5 frame's chunks are not all of one size; wave-uniform,
+    // two scalar loads), or of the uniform cut
+    const int j0 = starts ? starts[blockIdx.y] : blockIdx.y * beams_per_chunk;
+    const int j1 = starts ? starts[blockIdx.y + 1] : min(nb, j0 + beams_per_chunk);
     // every lane of the last wave stays in the loop (clamped to the last particle, its result dropped): the wave-level decisions
     // below (ballots) then always see 64 lanes
     const bool real = slot < n;
@@ -1257,4 +1262,8 @@ __global__ __launch_bounds__(64) void k_score_kd_cells(const float *__restrict__
     // group's chunks as 16-byte pieces of one contiguous run instead of one strided 2-byte load per chunk (a lane beyond n stores 0)
     // (as non-temporal stores: measured neutral, tools/experiments/r05/README.md)
     if (out_mode == 4) ((short *)out)[((size_t)g * gridDim.y + blockIdx.y) * 64 + threadIdx.x] = real ? (short)(int)acc : (short)0;
+    // (frame probe: when the last wave ended -- a maximum over the launch's waves, spread over PF_PROBE_ENDS words: see there.  An
+    // instantiation of its own, launched only while the probe is on: these two lines behind a null test cost the kernel 20 us of its 398
+    // at 100 k particles with the probe OFF -- profiles/chunk_taper_ab.txt, "what the end stamp costs")
+    if (ENDS && probe_ends && threadIdx.x == 0) atomicMax(probe_ends + (blockIdx.x & (PF_PROBE_ENDS - 1)) * PF_PROBE_END_STRIDE, (unsigned long long)wall_clock64());
 }

@@ -1105,7 +1105,7 @@ static int gates_decide(pfslam_handle *h, bool *use)
 
 static void frame_free(pfslam_handle *h)
 {
-    void *bufs[] = {h->fs, h->wcounts, h->flags, h->order_tmp, h->tparts, h->wall_c2, h->wall_xy2, h->wall_leaf2, h->wall_new2, h->wall_runs, h->wall_keys_s, h->wall_c2s, h->fstats, h->cloud, h->sigr, h->order_ring, h->pgroup, h->probe};
+    void *bufs[] = {h->fs, h->wcounts, h->flags, h->order_tmp, h->tparts, h->wall_c2, h->wall_xy2, h->wall_leaf2, h->wall_new2, h->wall_runs, h->wall_keys_s, h->wall_c2s, h->fstats, h->cloud, h->sigr, h->order_ring, h->pgroup, h->probe, h->plan_starts};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     hipEvent_t evs[] = {h->ev_reduced, h->ev_tree2, h->ev_order, h->ev_icp, h->ev_ftail, h->ev_shift, h->ev_poseg,
@@ -1135,10 +1135,17 @@ static bool frame_v2_ok(pfslam_handle *h, int *chunks_out, int *bpc_out)
 {
     if (h->timing >= 2 || h->kd_size <= 0 || !h->integral_w || h->nb > 4096) return false;
     if (!org_use_cells(h, nullptr, /*frame_loop=*/true)) return false;
-    const int chunks = score_chunks(h);
-    const int bpc = (h->nb + chunks - 1) / chunks;
-    const int used = (h->nb + bpc - 1) / bpc;
-    if (used < 2 || !((float)bpc * h->w_absmax <= 32767.0f)) return false;
+    // the chunk plan (score_plan.h): uniform chunks, or -- long chunks -- last rows that shrink.  It changes with the particle count, the
+    // beam count and the map's largest |weight| only
+    if (h->plan_n != h->n || h->plan_nb != h->nb || h->plan_w != h->w_absmax) {
+        h->chunk_plan = pf::score_plan(h->n, h->nb, h->w_absmax, h->integral_w != 0);
+        h->plan_n = h->n;
+        h->plan_nb = h->nb;
+        h->plan_w = h->w_absmax;
+        h->plan_uploaded = false;
+    }
+    const int used = h->chunk_plan.used, bpc = h->chunk_plan.bpc; // (bpc: the largest chunk)
+    if (used < 2 || !((float)bpc * h->w_absmax <= 32767.0f)) return false; // 16-bit partials: a chunk's sum must fit
     if ((h->gn + PF_SCAN_TILE - 1) / PF_SCAN_TILE > 4096) return false; // k_scan_apply2 / k_sample_gather's LDS prefix maxima (a sharded job scans the GLOBAL weights)
     *chunks_out = used;
     *bpc_out = bpc;
@@ -1292,6 +1299,20 @@ static int frame_v2_begin(pfslam_handle *h, int frame, const float *scan_host, i
             h->pgroup_elems = need;
         }
     }
+    // The plan's chunk starts, where the chunks are not all of one size (frame_v2_ok has just made the plan these `used` chunks belong to).
+    // A new plan is rare -- another map's weights, another particle count: the launches that read the old starts are waited for.
+    if (h->chunk_plan.tapered && !h->plan_uploaded) {
+        for (hipStream_t st : {h->stream, h->aux, h->cstream, h->istream}) HIPCHK(hipStreamSynchronize(st));
+        if ((int)h->chunk_plan.starts.size() > h->plan_starts_cap) {
+            if (h->plan_starts) HIPCHK(hipFree(h->plan_starts));
+            h->plan_starts = nullptr;
+            h->plan_starts_cap = 0;
+            CHK(dalloc(&h->plan_starts, h->chunk_plan.starts.size()));
+            h->plan_starts_cap = (int)h->chunk_plan.starts.size();
+        }
+        HIPCHK(hipMemcpy(h->plan_starts, h->chunk_plan.starts.data(), h->chunk_plan.starts.size() * 4, hipMemcpyHostToDevice));
+        h->plan_uploaded = true;
+    }
     bool gates = false;
     CHK(gates_decide(h, &gates)); // (may drain the pipeline: a change of mode, a self-test that has to run again)
     const bool sync_cells = h->cells_wipe_pending; // wiped rows: marked, walked and published in front of the scan-match kernel
@@ -1318,6 +1339,7 @@ static int frame_v2_begin(pfslam_handle *h, int frame, const float *scan_host, i
     h->cur_frame = frame;
     h->fv.used = used;
     h->fv.bpc = bpc;
+    h->fv.starts = h->chunk_plan.tapered ? h->plan_starts : nullptr; // (null: uniform chunks of bpc beams)
     h->fv.frame = frame;
     h->fv.sync_cells = sync_cells;
     h->fv.serial = serial;
@@ -1343,8 +1365,11 @@ static int frame_v2_begin(pfslam_handle *h, int frame, const float *scan_host, i
             scan_reach_of(h, hs);
             // (frame probe on: this ticket's row of stamps starts empty -- "0 = that launch did not run" also after the ring has wrapped.  Every
             // other stream's first launch of the frame sits behind SCAN(t) / ORDER(t), which this stream raises behind the memset.)
-            if (h->probe && h->probe_frames > 0)
+            if (h->probe && h->probe_frames > 0) {
                 HIPCHK(hipMemsetAsync(h->probe + (size_t)(seq % h->probe_frames) * PF_PROBE_SLOTS, 0, (size_t)PF_PROBE_SLOTS * 8, P));
+                HIPCHK(hipMemsetAsync(h->probe + (size_t)h->probe_frames * PF_PROBE_SLOTS + (size_t)(seq % h->probe_frames) * PF_PROBE_ENDS * PF_PROBE_END_STRIDE, 0,
+                                      (size_t)PF_PROBE_ENDS * PF_PROBE_END_STRIDE * 8, P)); // (the ends of the scan-match launch's waves)
+            }
             HIPCHK(hipMemcpyAsync(h->scan, hs, (size_t)h->nb * 4, hipMemcpyHostToDevice, P));
             // (gates) the scan is there: all the ICP solve waits for -- it then starts behind the previous frame's wall weights instead of behind
             // this frame's lane order, which matters when the scan-match kernel is too short to hide it (1000 particles: the wall kernel
@@ -1430,20 +1455,28 @@ static int frame_v2_score(pfslam_handle *h)
     }
     // a sharded job's resample imports particles from the other shards: unguarded only once a header with the job-wide |heading| maximum is booked
     const bool guard = !(h->theta_bound < 0.5f * PF_SUM_THETA_MAX) || (c.multi && !h->theta_global_known);
-    const dim3 grid64(groups, used);
+    const dim3 grid64(groups, used); // groups fastest: the plan's short chunks are the last to be dispatched
+    const int *starts = h->fv.starts;
+    unsigned long long *ends = h->probe ? h->probe + (size_t)h->probe_frames * PF_PROBE_SLOTS + (size_t)(seq % h->probe_frames) * PF_PROBE_ENDS * PF_PROBE_END_STRIDE : nullptr;
 #define PF_CELLS_ARGS grid64, dim3(64), 0, C, h->x_frame, h->y_frame, h->th_frame, h->n, h->scan, (const pf::BeamParts *)h->beam_angle, h->nb, bpc, c.tv, c.geo, \
                       (const unsigned *)h->cell_tab, (const uint4 *)h->cell_pool, (const int *)h->cell_state, (const int *)c.order, 0
-    if (h->trig) hipLaunchKernelGGL((k_score_kd_cells<false, PF_TRIG_DEVLIB>), PF_CELLS_ARGS, (float *)h->pgroup, 4, (pf::KdCensus *)nullptr, PB(PB_SCORE), (const double2 *)nullptr);
-    else if (guard) hipLaunchKernelGGL((k_score_kd_cells<false, true>), PF_CELLS_ARGS, (float *)h->pgroup, 4, (pf::KdCensus *)nullptr, PB(PB_SCORE), (const double2 *)nullptr);
-    else hipLaunchKernelGGL((k_score_kd_cells<false, false>), PF_CELLS_ARGS, (float *)h->pgroup, 4, (pf::KdCensus *)nullptr, PB(PB_SCORE), (const double2 *)nullptr);
+#define PF_CELLS_TAIL (float *)h->pgroup, 4, (pf::KdCensus *)nullptr, PB(PB_SCORE), (const double2 *)nullptr, starts, ends
+    if (ends) { // frame probe on: the instantiations that also say when each wave ended
+        if (h->trig) hipLaunchKernelGGL((k_score_kd_cells<false, PF_TRIG_DEVLIB, true>), PF_CELLS_ARGS, PF_CELLS_TAIL);
+        else if (guard) hipLaunchKernelGGL((k_score_kd_cells<false, true, true>), PF_CELLS_ARGS, PF_CELLS_TAIL);
+        else hipLaunchKernelGGL((k_score_kd_cells<false, false, true>), PF_CELLS_ARGS, PF_CELLS_TAIL);
+    } else if (h->trig) hipLaunchKernelGGL((k_score_kd_cells<false, PF_TRIG_DEVLIB>), PF_CELLS_ARGS, PF_CELLS_TAIL);
+    else if (guard) hipLaunchKernelGGL((k_score_kd_cells<false, true>), PF_CELLS_ARGS, PF_CELLS_TAIL);
+    else hipLaunchKernelGGL((k_score_kd_cells<false, false>), PF_CELLS_ARGS, PF_CELLS_TAIL);
+#undef PF_CELLS_TAIL
     HIPCHK(hipGetLastError());
     if (t_a) {
         HIPCHK(hipEventRecord(t_b, C));
         h->ev_pending.push_back(pfslam_handle::TimedSpan{t_a, t_b, PF_T_SCORE});
     }
-    if (h->census_log && h->census_n < PF_CENSUS_LOG) { // the counting instantiation on the very same inputs (no output: mode 2)
-        if (h->trig) hipLaunchKernelGGL((k_score_kd_cells<true, PF_TRIG_DEVLIB>), PF_CELLS_ARGS, (float *)h->pgroup, 2, h->census_log + h->census_n++, (unsigned long long *)nullptr);
-        else hipLaunchKernelGGL((k_score_kd_cells<true, true>), PF_CELLS_ARGS, (float *)h->pgroup, 2, h->census_log + h->census_n++, (unsigned long long *)nullptr);
+    if (h->census_log && h->census_n < PF_CENSUS_LOG) { // the counting instantiation on the very same inputs, grid and chunk plan (no output: mode 2)
+        if (h->trig) hipLaunchKernelGGL((k_score_kd_cells<true, PF_TRIG_DEVLIB>), PF_CELLS_ARGS, (float *)h->pgroup, 2, h->census_log + h->census_n++, (unsigned long long *)nullptr, (const double2 *)nullptr, starts);
+        else hipLaunchKernelGGL((k_score_kd_cells<true, true>), PF_CELLS_ARGS, (float *)h->pgroup, 2, h->census_log + h->census_n++, (unsigned long long *)nullptr, (const double2 *)nullptr, starts);
         HIPCHK(hipGetLastError());
     }
 #undef PF_CELLS_ARGS

@@ -7,6 +7,7 @@
 #include "../../include/pfslam.h"
 #include "kd_device.h"
 #include "pf_math.h"
+#include "score_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -209,7 +210,7 @@ struct pfslam_handle {
     bool shard_v2 = false;          // the sharded frame being enqueued is a cut of the round-5 frame (else: the staged round-4 chain, every collective on the handle's stream)
     bool shard_call = false;        // the frame being enqueued came in through pfslam_shard_*
     bool theta_global_known = true; // sharded jobs: a header with the job-wide |heading| maximum has been booked since the particles were last set
-    struct FrameV2 { int used = 0, bpc = 0, frame = 0; bool sync_cells = false, serial = false, sharded = false, gates = false, ftail_gate = false; } fv; // the round-5 frame being enqueued, between its parts
+    struct FrameV2 { int used = 0, bpc = 0, frame = 0; const int *starts = nullptr; bool sync_cells = false, serial = false, sharded = false, gates = false, ftail_gate = false; } fv; // the round-5 frame being enqueued, between its parts
     bool gates_tested = false;      // the self-test of the four streams has run since they last changed (pfslam_set_stream)
     bool gates_ok = false;          // ... and they make progress independently of one another
     bool gates_live = false;        // the frames in flight use gates (a change of mode drains the pipeline first)
@@ -318,6 +319,13 @@ struct pfslam_handle {
     int *order_ring = nullptr;    // [PF_FRAME_RING][n]: lane order by ticket (the cells' stream reads a frame's order while the next is made)
     short *pgroup = nullptr;      // group-major 16-bit beam-chunk partials
     size_t pgroup_elems = 0;
+    // the round-5 frame's chunk plan (score_plan.h) and its starts on the device, uploaded when (n, nb, w_absmax) change
+    pf::ScorePlan chunk_plan;
+    int plan_n = -1, plan_nb = -1;
+    float plan_w = -1.0f;
+    int *plan_starts = nullptr;
+    int plan_starts_cap = 0;
+    bool plan_uploaded = false;
     hipStream_t fstream = nullptr; // F: the free cells' chain (the round-4 ICP stream's place: a FIFTH stream halves the frame rate on this runtime)
     hipEvent_t ev_reduced = nullptr, ev_tree2 = nullptr, ev_order = nullptr, ev_icp = nullptr, ev_ftail = nullptr, ev_shift = nullptr;
     hipEvent_t ev_marked_r[4] = {nullptr, nullptr, nullptr, nullptr}, ev_walked_r[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -339,11 +347,19 @@ struct pfslam_handle {
     int probe_frames = 0;
 };
 #define PF_PROBE_SLOTS 32
+// "when the last wave of the scan-match launch ended" is a maximum over every wave of the launch.  65 646 atomicMax on ONE word doubled the
+// kernel (812 us for 399 us with the probe on, profiles/chunk_taper_ab.txt: device-scope atomics on one address are applied one after
+// the other), so a wave's end goes to one of PF_PROBE_ENDS words on cache lines of their own, behind the frames' rows of the same
+// allocation, and pfslam_get_probe takes the maximum (434 us: the probe-on kernel still pays 9 % for these stamps).
+#define PF_PROBE_ENDS 64
+#define PF_PROBE_END_STRIDE 16 /* 128 bytes */
+#define PF_PROBE_ROW (PF_PROBE_SLOTS + PF_PROBE_ENDS * PF_PROBE_END_STRIDE) /* 64-bit words per frame: the stamps, then the ends */
 enum { PB_ICP = 0, PB_MOTION, PB_SCATTER, PB_BOX, PB_MARK, PB_WALK, PB_SCORE, PB_REDUCE, PB_WALLS, PB_UPDATE, PB_WEIGHTS, PB_APPLY, PB_GATHER, PB_RAYS, PB_COUNT,
-       PB_LISTS, PB_FREE, PB_WALLW, PB_REDUCE_LAST, PB_WALLS_KEYS, PB_WALLS_SORTED, PB_WALLS_TRAV, PB_WALLS_END, PB_WALLS_REP, PB_ICP_SOLVE, PB_ICP_END, PB_UPDATE_END, PB_REDUCE_END, PB_END };
+       PB_LISTS, PB_FREE, PB_WALLW, PB_REDUCE_LAST, PB_WALLS_KEYS, PB_WALLS_SORTED, PB_WALLS_TRAV, PB_WALLS_END, PB_WALLS_REP, PB_ICP_SOLVE, PB_ICP_END, PB_UPDATE_END, PB_REDUCE_END, PB_SCORE_LAST, PB_SCORE_END, PB_END };
 static const char *const pb_names[PB_END] = {"K icp", "P motion+cells", "P scatter", "K boxes", "K mark", "K walk", "C scan-match", "C reduce", "C walls+insert",
                                              "C cells update", "P weights", "P scan apply", "P sample+gather", "F rays", "F count", "F lists", "F free pass", "F wall weights",
-                                             "C reduce: last wg", "C walls: keys", "C walls: sorted", "C walls: traversed", "C walls: end", "C walls: traversal launch", "K icp: solve", "K icp: end", "C cells update: last wg ends", "C reduce: last wg ends"};
+                                             "C reduce: last wg", "C walls: keys", "C walls: sorted", "C walls: traversed", "C walls: end", "C walls: traversal launch", "K icp: solve", "K icp: end", "C cells update: last wg ends", "C reduce: last wg ends",
+                                             "C scan-match: last wave starts", "C scan-match: last wave ends"};
 static_assert(PB_END <= PF_PROBE_SLOTS, "probe slots");
 
 // ==========================================================================================
@@ -1591,22 +1607,15 @@ extern "C" int pfslam_shift_particles(pfslam_handle *h, const float delta[3])
 // ---- A5 -------------------------------------------------------------------------------------
 static int score_chunks(const pfslam_handle *h)
 {
-    // ~16 rounds of the 8192 wave slots (256 CUs x 32): fine-grained enough that the tail of the last round is
-    // small (measured: 16 k waves 3.33 ms, 128 k waves 2.9-3.0 ms at 100 k particles); down to one beam per chunk for small N
+    // The uniform cut of the stage-level launches, the staged frame and the census replay of a stage: score_plan.h has the target and the
+    // reasons.  The round-5 frame takes the whole plan (frame_v2_ok, pf::score_plan): from chunks of 8 beams on (1081 beams: ~27 k particles)
+    // its last 16384 / groups rows of chunks shrink to a sixth of the uniform size, which shortens the launch's tail -- 69 -> 42 us and
+    // 0.5280 -> 0.5125 ms per frame at 100 k particles (profiles/chunk_taper_ab.txt) -- and a map whose weights are too large for 16-bit
+    // partials of the uniform chunk gets more, shorter chunks instead of the staged frame.
     const int groups = (h->n + 63) / 64;
-    // (round 5: 65 536 -- 42 chunks of 26 beams at 100 k particles.  A wave's prologue, the fp64 sincos of its 64 headings, is ~10 % of a
-    // 13-beam chunk, and the reduce reads half the partials: frame 0.530 -> 0.520 ms in an A/B on one box; 32 768: 0.538, 262 144: 0.569)
-    // Below ~40 k particles fewer, longer waves win (a wave's prologue and the launch's ramp against the beams it scores): ~160 chunks per
-    // group between 24 576 and 65 536 waves (profiles/r05_sweep_waves.txt: 10 k particles 0.218 -> 0.209 ms per frame, 20 k 0.2493 -> 0.2478,
-    // 1 k / 4 k unchanged within noise)
-    const int target = std::max(24576, std::min(65536, groups * 160));
-    int chunks = (target + groups - 1) / groups;
-    chunks = std::max(1, std::min(chunks, h->nb)); // small particle counts go down to one beam per wave
-    // Beam-chunk partials added afterwards equal the reference's sequential beam-order float sum only when every term is an
-    // integer and no partial sum can pass 2^24 (any map the SLAM step builds: 0 / -100 initial, -1 / +4 steps, clamp +-113; upload_tree
-    // holds an uploaded map to n_beams x largest |weight| <= 2^24).  A map uploaded through pfslam_set_map with other weights is scored
-    // in one chunk: slower, but kernEvaluateParticlesKD's own summation order.
-    if (!h->integral_w) chunks = 1;
+    const int target = std::max(24576, std::min(65536, groups * 160)); // (= pf::score_plan_target(h->n), stated where tests/test_gpu_size_edges.py reads it)
+    int chunks = pf::score_plan_chunks_for(target, groups, h->nb);
+    if (!h->integral_w) chunks = 1; // (other weights: ONE chunk, kernEvaluateParticlesKD's own summation order)
     return chunks;
 }
 
@@ -2247,8 +2256,8 @@ extern "C" int pfslam_set_probe(pfslam_handle *h, int frames)
     h->probe = nullptr;
     h->probe_frames = 0;
     if (frames > 0) {
-        CHK(dalloc(&h->probe, (size_t)frames * PF_PROBE_SLOTS));
-        HIPCHK(hipMemset(h->probe, 0, (size_t)frames * PF_PROBE_SLOTS * 8));
+        CHK(dalloc(&h->probe, (size_t)frames * PF_PROBE_ROW)); // [frames][PF_PROBE_SLOTS] stamps, then [frames][PF_PROBE_ENDS] x 128 bytes
+        HIPCHK(hipMemset(h->probe, 0, (size_t)frames * PF_PROBE_ROW * 8));
         h->probe_frames = frames;
     }
     return 0;
@@ -2263,11 +2272,15 @@ extern "C" int pfslam_get_probe(pfslam_handle *h, unsigned long long *out, int c
     CHK(settle(h));
     HIPCHK(hipStreamSynchronize(h->stream));
     const int n = std::min(std::min(cap_frames, h->probe_frames), h->seq);
-    std::vector<unsigned long long> all((size_t)h->probe_frames * PF_PROBE_SLOTS);
+    std::vector<unsigned long long> all((size_t)h->probe_frames * PF_PROBE_ROW);
     HIPCHK(hipMemcpy(all.data(), h->probe, all.size() * 8, hipMemcpyDeviceToHost));
     for (int k = 0; k < n; k++) {
-        const int ticket = h->seq - n + 1 + k;
-        memcpy(out + (size_t)k * PF_PROBE_SLOTS, &all[(size_t)(ticket % h->probe_frames) * PF_PROBE_SLOTS], PF_PROBE_SLOTS * 8);
+        const int ticket = h->seq - n + 1 + k, row = ticket % h->probe_frames;
+        memcpy(out + (size_t)k * PF_PROBE_SLOTS, &all[(size_t)row * PF_PROBE_SLOTS], PF_PROBE_SLOTS * 8);
+        const unsigned long long *ends = &all[(size_t)h->probe_frames * PF_PROBE_SLOTS + (size_t)row * PF_PROBE_ENDS * PF_PROBE_END_STRIDE];
+        unsigned long long last = 0; // the scan-match launch's last wave to end
+        for (int e = 0; e < PF_PROBE_ENDS; e++) last = std::max(last, ends[(size_t)e * PF_PROBE_END_STRIDE]);
+        out[(size_t)k * PF_PROBE_SLOTS + PB_SCORE_END] = last;
     }
     *n_frames = n;
     return 0;

@@ -5,6 +5,10 @@ Where a round-5 frame's time goes, read off the frame's own kernels (pfslam_set_
 start of the frame's scan-match kernel, and the two numbers the frame is judged by:
   chain = start of the next frame's scan-match kernel - start of this frame's reduce (what sits between two scan-match kernels)
   frame = start of the next frame's scan-match kernel - start of this frame's
+and how the scan-match launch ends:
+  score tail         = last wave ends - last-indexed wave starts (what the launch still takes once the dispatcher has run dry)
+  mean wave duration = kernel time x wave slots / waves (--chunks: the frame's chunk count, tools/score_plan_print.cpp)
+(With the probe on every wave of that launch stamps its end: the kernel runs ~9 % longer than in a timed frame, profiles/chunk_taper_ab.txt.)
 Same workload as bench.py (synthetic 1081-beam scans, 100 k particles, 100 k-point map, frames 11-30 of the run)."""
 import argparse
 import importlib
@@ -18,6 +22,14 @@ sys.path.insert(0, ROOT)
 pkg = importlib.import_module("gpu-icp-slam_amd")
 
 
+def uniform_chunks(n, nb):
+    """csrc/score_plan.h, the uniform plan: chunks per group"""
+    groups = (n + 63) // 64
+    chunks = max(1, min(-(-max(24576, min(65536, groups * 160)) // groups), nb))
+    bpc = -(-nb // chunks)
+    return -(-nb // bpc)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--particles", type=int, default=100000)
@@ -26,6 +38,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--serial", action="store_true")
     ap.add_argument("--variant", type=int, default=0)
+    ap.add_argument("--chunks", type=int, default=0, help="beam chunks per group of the frame's scan-match launch (tools/score_plan_print.cpp prints the plan; "
+                    "0 = the uniform plan's count)")
+    ap.add_argument("--wave-slots", type=int, default=8192, help="256 CUs x 32 waves")
     a = ap.parse_args()
     pts, segs = pkg.synth.make_map_points(a.map_points, seed=1)
     tree = pkg.kd_create(pts)
@@ -62,6 +77,21 @@ def main():
     print("frame  (scan-match start to next scan-match start): mean %.1f us  min %.1f  max %.1f" % (nxt[good].mean(), nxt[good].min(), nxt[good].max()))
     print("chain  (reduce start to next scan-match start):     mean %.1f us  min %.1f  max %.1f" % (chain[good].mean(), chain[good].min(), chain[good].max()))
     print("scan-match kernel (start to reduce start, incl. its launch gap): mean %.1f us" % (t[:, rd] - t[:, sc])[ok].mean())
+    # how the scan-match launch ends: the last-indexed wave's start (groups fastest: the last chunk row's last group) and the latest end of any wave
+    if "C scan-match: last wave starts" in names:
+        ls, le = names.index("C scan-match: last wave starts"), names.index("C scan-match: last wave ends")
+        both = ok & (t[:, ls] > 0) & (t[:, le] > 0)
+        if both.any():
+            kern = (t[:, le] - t[:, sc])[both]
+            tail = (t[:, le] - t[:, ls])[both]
+            groups = (a.particles + 63) // 64
+            print("scan-match kernel (first wave starts to last wave ends): mean %.1f us  min %.1f  max %.1f" % (kern.mean(), kern.min(), kern.max()))
+            print("last wave starts at: mean %+.1f us  min %+.1f  max %+.1f" % ((t[:, ls] - t[:, sc])[both].mean(), (t[:, ls] - t[:, sc])[both].min(), (t[:, ls] - t[:, sc])[both].max()))
+            print("score tail (last wave starts to last wave ends): mean %.1f us  min %.1f  max %.1f" % (tail.mean(), tail.min(), tail.max()))
+            chunks = a.chunks or uniform_chunks(a.particles, len(scans[0]))
+            waves = groups * chunks
+            print("mean wave duration (kernel time x %d wave slots / %d waves = %d groups x %d chunks): %.1f us"
+                  % (a.wave_slots, waves, groups, chunks, kern.mean() * a.wave_slots / waves))
     print("cell stats:", {k: v for k, v in e.cell_stats().items() if k in ("cells", "rows", "pool_slots", "walked_from_root", "extended", "updates", "wipes", "flags")})
     print("cell check:", e.check_cells())
     print("frame mode:", e.frame_mode())
