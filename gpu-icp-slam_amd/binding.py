@@ -28,6 +28,7 @@ SYMBOLS = [
     "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_estimate", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
     "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch", "pfslam_search", "pfslam_search_default_opts", "pfslam_search_scan", "pfslam_search_wide",
     "pfslam_search_cov", "pfslam_search_scan_cov", "pfslam_search_cov_default_opts", "pfslam_search_best", "pfslam_search_best_default_opts",
+    "pfslam_cast", "pfslam_cast_default_opts", "pfslam_map_raster",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
 
@@ -62,6 +63,12 @@ class CovOpts(C.Structure):
 class BestOpts(C.Structure):
     """pfslam_best_opts (include/pfslam.h)."""
     _fields_ = [("count", C.c_int32), ("tile_log2", C.c_int32), ("group_theta", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class CastOpts(C.Structure):
+    """pfslam_cast_opts (include/pfslam.h)."""
+    _fields_ = [("max_range", C.c_float), ("w_min", C.c_float), ("no_hit", C.c_float), ("inflate", C.c_int32), ("skip_cells", C.c_int32),
+                ("reserved_", C.c_int32 * 3)]
 
 
 REGISTER_STATUS = {0: "max_iters", 1: "converged", 2: "too_few_pairs", 3: "not_finite"}
@@ -185,6 +192,10 @@ def load():
     L.pfslam_search_best_default_opts.restype = None
     L.pfslam_search_best_default_opts.argtypes = [vp]
     L.pfslam_search_best.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pfslam_cast_default_opts.restype = None
+    L.pfslam_cast_default_opts.argtypes = [vp]
+    L.pfslam_cast.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.pfslam_map_raster.argtypes = [vp, vp, vp, vp, C.c_size_t]
     L.pfslam_debug_check_cells.argtypes = [vp, vp]
     L.pfslam_set_probe.argtypes = [vp, i32]
     L.pfslam_get_probe.argtypes = [vp, vp, i32, vp, vp]
@@ -691,6 +702,50 @@ class PfSlam:
         if scores:
             out["scores"] = vol
         return out
+
+    def _cast_opts(self, who, opts):
+        o = CastOpts()
+        self.L.pfslam_cast_default_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("max_range", "w_min", "no_hit", "inflate", "skip_cells"):
+                raise TypeError("%s() has no option %r" % (who, k))
+            setattr(o, k, v)
+        return o
+
+    def cast(self, poses=None, cells=False, **opts):
+        """The scan the map predicts from each of the m x 3 `poses` (None: the handle's pose), by a walk of every beam through a raster
+        of the map's nodes (include/pfslam.h, pfslam_cast).  Options by name (max_range, w_min, no_hit, inflate, skip_cells) over
+        pfslam_cast_default_opts.  Returns ranges (m x n_beams float32), cells (m x n_beams x 2 int32 with cells=True, else None; a miss
+        is INT32_MIN twice) and stats (int64[8]: rays, hits, qualifying nodes, occupied cells, x0, y0, W, H).  Reads the handle's map,
+        writes none of its state."""
+        o = self._cast_opts("cast", opts)
+        ps = None
+        m = 1
+        if poses is not None:
+            ps = np.ascontiguousarray(poses, dtype=np.float32)
+            if ps.ndim == 1 and ps.size == 3:
+                ps = ps.reshape(1, 3)
+            if ps.ndim != 2 or ps.shape[1] != 3:
+                raise ValueError("cast(): poses must be m x (x, y, theta), got shape %r" % (ps.shape,))
+            m = len(ps)
+        rows = m if m * self.nb <= 1 << 24 else 0      # (a larger call is the library's to refuse)
+        ranges = np.zeros((rows, self.nb), np.float32)
+        ce = np.zeros((rows, self.nb, 2), np.int32) if cells else None
+        stats = np.zeros(8, np.int64)
+        _chk(self.L.pfslam_cast(self._h, None if ps is None else _p(ps), m, C.byref(o), _p(ranges), None if ce is None else _p(ce), _p(stats)), "pfslam_cast")
+        return {"ranges": ranges, "cells": ce, "stats": stats}
+
+    def map_raster(self, **opts):
+        """The occupancy raster pfslam_cast walks through (include/pfslam.h, pfslam_map_raster; cast()'s options): (box, occ) with
+        box = (x0, y0, W, H) in cells and occ a W x H uint8 array, occ[kx - x0, ky - y0] = 1 for an occupied cell."""
+        o = self._cast_opts("map_raster", opts)
+        stats = np.zeros(8, np.int64)
+        _chk(self.L.pfslam_map_raster(self._h, C.byref(o), _p(stats), None, 0), "pfslam_map_raster")
+        W, H = int(stats[6]), int(stats[7])
+        occ = np.zeros((W, H), np.uint8)
+        if W * H:
+            _chk(self.L.pfslam_map_raster(self._h, C.byref(o), _p(stats), _p(occ), W * H), "pfslam_map_raster")
+        return tuple(int(v) for v in stats[4:8]), occ
 
     def _cov_opts(self, sigma):
         q = CovOpts()

@@ -183,6 +183,13 @@ struct pfslam_handle {
     float *cov_part = nullptr;
     size_t cov_part_cap = 0;
     unsigned long long *cov_state = nullptr;
+    // pfslam_cast's / pfslam_map_raster's own buffers, allocated on first use and grown like pfslam_search's: the raster's 8 x 8-cell tiles,
+    // the uploaded poses (m x 3), the ranges and hit cells of a call, pfslam_map_raster's bytes, and box words + counts
+    unsigned long long *cast_tiles = nullptr;
+    float *cast_poses = nullptr, *cast_ranges = nullptr;
+    int *cast_cells = nullptr, *cast_state = nullptr;
+    uint8_t *cast_occ = nullptr;
+    size_t cast_tiles_cap = 0, cast_poses_cap = 0, cast_ranges_cap = 0, cast_cells_cap = 0, cast_occ_cap = 0;
     float *est_part = nullptr; // pfslam_estimate: 11 tile sums per 4096-particle tile of the GLOBAL cloud, then the 16 output floats
     // grid path
     int8_t *grid = nullptr;
@@ -1084,7 +1091,7 @@ extern "C" int pfslam_destroy(pfslam_handle *h)
                     h->fit, h->fit_i, h->partial, h->mkey, h->order2, h->cells, h->stats, h->pose, h->start, h->icp_tar, h->icp_cor, h->icp_dbg,
                     h->free_mask, h->blk_cnt, h->wall_cell, h->free_cell, h->wall_pts, h->free_pts,
                     h->wall_c, h->free_c, h->counts, h->tile_r, h->tile_r2, h->sums, h->cdf,
-                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->srch_field, h->srch_ends, h->srch_nin, h->srch_scores, h->srch_state, h->wide_field, h->wide_ends, h->wide_nin, h->wide_nodes, h->wide_lb, h->wide_state, h->best_tab, h->best_list, h->best_state, h->scan_in, h->scan_pts, h->scan_state, h->cov_part, h->cov_state, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
+                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->srch_field, h->srch_ends, h->srch_nin, h->srch_scores, h->srch_state, h->wide_field, h->wide_ends, h->wide_nin, h->wide_nodes, h->wide_lb, h->wide_state, h->best_tab, h->best_list, h->best_state, h->scan_in, h->scan_pts, h->scan_state, h->cov_part, h->cov_state, h->cast_tiles, h->cast_poses, h->cast_ranges, h->cast_cells, h->cast_state, h->cast_occ, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (h->own_global) {
@@ -2495,3 +2502,4 @@ static int frame_v2_finish(pfslam_handle *h);
 #include "pfslam_search_cov.hip.inc"
 #include "pfslam_search_wide.hip.inc"
 #include "pfslam_search_best.hip.inc"
+#include "pfslam_cast.hip.inc"

@@ -317,6 +317,20 @@ bool pfslamSearch(glm::vec3 centre, glm::vec3 &pose, int *index)
     if (index) *index = (int)info[1];
     return true;
 }
+bool pfslamCastScan(glm::vec3 pose, float *ranges, int *hits)
+{
+    if (!g_handle || !ranges) return false;
+    pfslam_cast_opts o;
+    pfslam_cast_default_opts(&o);
+    const float p[3] = {pose.x, pose.y, pose.z};
+    int64_t stats[8];
+    if (pfslam_cast(g_handle, p, 1, &o, ranges, nullptr, stats)) { // (an empty map is a state of the filter, not a failure of the program)
+        fprintf(stderr, "pfslamCastScan: %s\n", pfslam_last_error());
+        return false;
+    }
+    if (hits) *hits = (int)stats[1];
+    return true;
+}
 bool pfslamSearchScan(const float *ref_scan, glm::vec3 ref_pose, glm::vec3 &pose, int *index, const float *scan)
 {
     if (!g_handle) return false;

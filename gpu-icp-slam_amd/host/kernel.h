@@ -106,6 +106,11 @@ bool pfslamSearchWide(glm::vec3 centre, float half_metres, float half_radians, g
 // cells hold a candidate, 0 when no heading has an in-range beam), or -1 (and a line on stderr): no live filter, no map yet, a count or a
 // window beyond the entry point's caps; the outputs are then untouched.  index may be null.
 int pfslamSearchBest(glm::vec3 centre, float half_metres, float half_radians, int count, glm::vec3 *poses, long long *index);
+// The scan the live filter's map predicts from `pose` (no reference counterpart; include/pfslam.h, pfslam_cast, the default options: a
+// node with w >= 1 occupies its cell and the eight around it, 30 m): ranges[1081], 30 for a beam that hits nothing; *hits the beams that
+// hit.  Reads the filter, changes nothing in it; like getPCData it first waits for the frames in flight.  hits may be null.  false (and a
+// line on stderr): no live filter or no map yet; the outputs are then untouched.
+bool pfslamCastScan(glm::vec3 pose, float *ranges, int *hits);
 // Map export for an end-to-end comparison: the point-cloud map as the reference's viewer filters it
 // (nodes with w > -100, main.cpp:269-284) -> PREFIX.kd.bin (float x, y, z, w per point, in node order) + PREFIX.kd.csv, and
 // the 2-D occupancy grid -> PREFIX.grid.i8 (dim.x * dim.y signed bytes, cell (x, y) at x * dim.x + y) + PREFIX.grid.pgm

@@ -1,5 +1,5 @@
 // replay_main.cpp -- headless counterpart of the reference's main loop (main.cpp:47-96, 175-229):
-//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [export=PREFIX]
+//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [cast=1] [export=PREFIX]
 //     grid           the 2-D occupancy-grid stages instead of the point-cloud ones
 //     loop           UpdateTopology + CheckLoopClosure at the end of every frame (kernel.cu:1750-1751, commented out in
 //                    the reference's shipped step); loop-closure proposals are printed per frame
@@ -21,21 +21,26 @@
 //                    the previous frame's pose (the default window around it); a line "odometry <frame> index <k> delta <dx dy dtheta> bits
 //                    <3 hex words of the winning pose>" and pfslamShiftParticles with that delta before the step ("odometry <frame> none"
 //                    and no shift when the call fails or no heading has an in-range beam)
+//     cast=1         a further line per frame: "cast <frame> hits <n> agree <k>": pfslamCastScan from the frame's pose through the frame's map,
+//                    the beams that hit, and the beams whose cast range is within 0.1 m of the scan's ("cast <frame> none" when the call fails or
+//                    the scan does not have the filter's 1081 beams)
 //     export=PREFIX  after the last frame: the map as the reference's viewer filters it (KD nodes with w > -100,
 //                    main.cpp:269-284) and the occupancy grid -> PREFIX.kd.bin / .kd.csv / .grid.i8 / .grid.pgm
 // iteration 0: Free + Init; then particleFilter(pbo=NULL, ++iteration, lidar) until the scans run out.
 // Prints one line per frame (pose, map size) and the mean step time.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 #include "kernel.h"
 
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [export=PREFIX]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [cast=1] [export=PREFIX]\n", argv[0]);
         return 1;
     }
     Scene *scene = new Scene(argv[1]);
@@ -43,7 +48,7 @@ int main(int argc, char **argv)
     size_t last = lidar->scans.size() - 1;
     bool loop = false, estimate = false;
     int register_iters = 0, multistart_iters = 0, search = 0;
-    bool odometry = false;
+    bool odometry = false, cast = false;
     std::string export_prefix;
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "grid") == 0) pfslamUseGridMap(true);
@@ -54,6 +59,7 @@ int main(int argc, char **argv)
         else if (strncmp(argv[i], "multistart=", 11) == 0) multistart_iters = atoi(argv[i] + 11);
         else if (strncmp(argv[i], "search=", 7) == 0) search = atoi(argv[i] + 7);
         else if (strncmp(argv[i], "odometry=", 9) == 0) odometry = atoi(argv[i] + 9) != 0;
+        else if (strncmp(argv[i], "cast=", 5) == 0) cast = atoi(argv[i] + 5) != 0;
         else if (strncmp(argv[i], "export=", 7) == 0) export_prefix = argv[i] + 7;
         else if (atoi(argv[i]) > 0) last = std::min(last, (size_t)atoi(argv[i]));
     }
@@ -171,6 +177,17 @@ int main(int argc, char **argv)
                 printf("search_best %zu %d index %lld pose %.6f %.6f %.6f bits %08x %08x %08x\n", iteration, n, index[n], r[n].x, r[n].y, r[n].z, b[0], b[1], b[2]);
             }
             if (found <= 0) printf("search_best %zu none\n", iteration);
+        }
+        if (cast) {
+            std::vector<float> expected(lidar->scans[iteration].size());
+            int hits = 0;
+            if (expected.size() == 1081 && pfslamCastScan(pos, expected.data(), &hits)) {
+                int agree = 0;
+                for (size_t b = 0; b < expected.size(); b++) agree += fabsf(expected[b] - lidar->scans[iteration][b]) <= 0.1f ? 1 : 0;
+                printf("cast %zu hits %d agree %d\n", iteration, hits, agree);
+            } else {
+                printf("cast %zu none\n", iteration);
+            }
         }
     }
     printf("mean step+readback %.3f ms over %zu frames\n", iteration ? total_ms / iteration : 0.0, iteration);

@@ -201,6 +201,15 @@ class ShardedSlam:
         the map and the scan are replicated, so every rank gets the unsharded bits with no collective."""
         return self.eng.search_best(centre, count=count, tile_log2=tile_log2, group_theta=group_theta, **opts)
 
+    def cast(self, poses=None, cells=False, **opts):
+        """The scan the map predicts from a list of poses (pfslam_cast): passed through like search -- the map is replicated, so every
+        rank gets the unsharded bits with no collective."""
+        return self.eng.cast(poses, cells, **opts)
+
+    def map_raster(self, **opts):
+        """The occupancy raster pfslam_cast walks through (pfslam_map_raster): passed through like cast."""
+        return self.eng.map_raster(**opts)
+
     def _all_gather(self, dst, src, which):
         """Collective `which` (0 pose blocks, 1 keys, 2 weights) of the frame being enqueued, in the stream the engine names for it
         (GPU engines: pfslam_shard_stream -- stream order is all the ordering there is; gloo completes it before it returns)."""

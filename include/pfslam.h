@@ -34,6 +34,7 @@
  *   pfslam_search_cov, _scan_cov       no counterpart: either search, plus the weighted mean pose, 3x3 covariance and Neff of its score volume
  *   pfslam_search_wide                 no counterpart: the same winner over windows of up to 2^31 - 1 candidates, by branch and bound
  *   pfslam_search_best                 no counterpart: the best candidate of each of the N best cells of such a window, by the same descent
+ *   pfslam_cast, pfslam_map_raster     no counterpart: the ranges the map predicts for a scan from any pose, by a walk through a raster of its nodes; that raster
  *   pfslam_topology_update, find_walls,
  *   check_loop_closure, get_topology   UpdateTopology / FindWalls / CheckLoopClosure   kernel.cu:623-795
  *   pfslam_shard_disperse / score / weights / finish   particleFilter split where a multi-GPU caller places its three
@@ -774,6 +775,67 @@ void pfslam_search_best_default_opts(pfslam_best_opts *opts);
 int pfslam_search_best(pfslam_handle *h, const float centre[3] /* NULL = the handle's pose */, const pfslam_search_opts *opts,
                        const pfslam_best_opts *best, float *poses_out /* count x 3 */, float *info /* count x 8 */,
                        int64_t *index /* count */, int *found, int64_t stats[8] /* may be NULL */);
+/* pfslam_cast / pfslam_map_raster: the scan the point-cloud map PREDICTS from a pose (no reference counterpart).  Every other question
+ * the library answers about its map is an end-point question ("how close is this beam's end to a node"); this one walks each beam through
+ * an occupancy raster of the nodes until it meets an occupied cell.  It gives per-beam residuals between a measured and an expected
+ * range (a beam through a mapped wall still ends "near a point"), a beam-model check of the poses pfslam_search_best and
+ * pfslam_register_batch return, visibility on the KD path, and an occupancy raster of the map for export.
+ *   max_range   m; finite, > 0; max_range / map_res_x and max_range / map_res_y both <= 16384
+ *   w_min       a node takes part iff w >= w_min (false for a NaN weight); finite
+ *   no_hit      the range reported for a ray that hits nothing; any float
+ *   inflate     0 .. 8: a node occupies the (2 inflate + 1)^2 cells around its own
+ *   skip_cells  >= 0: the first cell index of the walk that can be a hit (0 = the robot's own cell)
+ *   reserved_   must be 0
+ * All arithmetic is float, one rounding per operation, in the order written, no contraction; fdiv and fsqrt are the correctly rounded
+ * division and square root; integers are exact.  res_x = map_res_x, res_y = map_res_y (they may differ: nothing here needs square cells).
+ *   raster      a node (x, y, z, w) has the cell nx = rintf(fdiv(x, res_x)), ny = rintf(fdiv(y, res_y)); z is ignored.  It qualifies iff
+ *               w >= w_min && |nx| <= 2^20 && |ny| <= 2^20 (each false for a NaN).  The occupied set O holds the cells (kx, ky) for which
+ *               some qualifying node has |kx - nx| <= inflate && |ky - ny| <= inflate.  The box x0, y0, W, H is the bounding box of the
+ *               qualifying cells grown by inflate.  With no qualifying node the box is {0, 0, 0, 0}, every ray misses, the call succeeds.
+ *   ray         of pose (x, y, theta) and beam b: (wx, wy) = CleanLidarScan(b, max_range, theta) (it honours pfslam_set_trig);
+ *               sx = rintf(fdiv(x, res_x)), ex = rintf(fdiv(x + wx, res_x)), sy and ey likewise.  The ray misses if one of the four is
+ *               not finite or lies beyond +-2^20.  dx = ex - sx, dy = ey - sy, n = max(|dx|, |dy|); with n == 0 the ray misses.
+ *   walk        anchored at the robot, every cell a closed form of its index t, t = skip_cells .. n:
+ *                 |dx| >= |dy|:  kx = sx + sgn(dx) t,  ky = sy + sgn(dy) ((2 t |dy| + n) div (2 n))
+ *                 otherwise:     ky = sy + sgn(dy) t,  kx = sx + sgn(dx) ((2 t |dx| + n) div (2 n))
+ *               (the products stay below 2^31 by the bound on max_range).  The hit is the smallest t whose cell is in O.
+ *   range       fsqrt(ddx * ddx + ddy * ddy) with ddx = (float)kx * res_x - x, ddy = (float)ky * res_y - y.  A ray that misses reports
+ *               no_hit and the cell (INT32_MIN, INT32_MIN).
+ *   outputs     ranges_out[r * n_beams + b]; cells_out[(r * n_beams + b) * 2 + {0, 1}] = kx, ky; stats: [0] rays, [1] hits,
+ *               [2] qualifying nodes, [3] |O|, [4..7] x0, y0, W, H -- all eight are specified values.
+ * pfslam_map_raster builds the same raster: stats as above with [0] = [1] = 0, occ[(kx - x0) * H + (ky - y0)] = 1 iff (kx, ky) is in O.
+ * occ == NULL returns the stats only (the two-call pattern: ask for W and H, allocate, ask again).
+ * Refused (non-zero, pfslam_last_error names the cause under the function's name, outputs untouched): a NULL handle, opts or ranges_out
+ * (pfslam_map_raster: a NULL stats); m outside 1 .. 65536 or m * n_beams > 2^24; poses == NULL with m != 1; an option outside its range
+ * or reserved_ non-zero; no map; W * H > 2^28 (found on the device: one extra wait, like pfslam_search_wide's); cap < W * H.  A pose that
+ * is not finite is not refused: all of its rays miss.
+ * Method.  One thread per node merges the box into four biased words with atomicMax (k_search_ends' scheme) and counts the qualifying
+ * nodes; the host reads the words (the extra wait) and sizes the raster: 8 x 8-cell tiles of one 64-bit word each.  A clear, then one
+ * thread per node ORs the node's cells into at most 3 x 3 tiles (an OR is exact in any order), then a count of |O|.  The cast is one lane
+ * per ray, adjacent lanes the adjacent beams of one pose.  Because every cell is a closed form of t a ray jumps: to the first t inside
+ * the box (a start outside enters by it), and out of every empty tile to the first t that leaves it along either axis; inside a tile
+ * that holds something it steps cell by cell.  How the hit is found is no part of the specification.  Measured: profiles/cast.txt.
+ * Like every entry point but the step functions both calls first book the frames in flight and then run on the handle's stream.  They
+ * read the device-resident map and, for poses == NULL, the pose (on the device).  They write no state another entry point reads: not the
+ * pose, the particles, the tree, the 2-D grid, buffers 11 / 12 or the search buffers.  The raster, the pose list and the outputs are
+ * buffers of their own: they belong to the handle, are allocated on first use, grow when a call needs more and go with pfslam_destroy.
+ * Every call rebuilds the raster (the map changes every frame).  The map of a sharded handle is replicated: every rank gets the
+ * unsharded bits. */
+typedef struct pfslam_cast_opts {
+    float   max_range;
+    float   w_min;
+    float   no_hit;
+    int32_t inflate;
+    int32_t skip_cells;
+    int32_t reserved_[3];
+} pfslam_cast_opts;
+/* {30.0f, 1.0f, 30.0f, 1, 1, {0, 0, 0}} */
+void pfslam_cast_default_opts(pfslam_cast_opts *o);
+int pfslam_cast(pfslam_handle *h, const float *poses /* m x 3; NULL = the handle's pose, m must be 1 */, int m,
+                const pfslam_cast_opts *opts, float *ranges_out /* m x n_beams */,
+                int32_t *cells_out /* NULL or m x n_beams x 2 */, int64_t stats[8] /* may be NULL */);
+int pfslam_map_raster(pfslam_handle *h, const pfslam_cast_opts *opts, int64_t stats[8],
+                      uint8_t *occ /* NULL or W * H bytes */, size_t cap);
 /* ---- round-5 frame loop: test and measurement support (no reference counterpart) ----
  * pfslam_set_serial(h, 1): every launch of every frame on ONE stream, in the order the four chains of a frame are enqueued (what the
  * environment variable PFSLAM_SERIAL=1 sets at creation).  Results and the cell rows' bookkeeping are the same as with the chains on their
