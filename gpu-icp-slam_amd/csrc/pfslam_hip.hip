@@ -15,6 +15,7 @@
 #include <atomic>
 #include <deque>
 #include <thread>
+#include <type_traits>
 #include <cmath>
 #include <cstdio>
 #include <chrono>
@@ -154,8 +155,10 @@ struct pfslam_handle {
     float *reg_tar = nullptr, *reg_cor = nullptr, *reg_out = nullptr; // pfslam_register's own scratch (allocated on first use): targets, correspondences, pose + info + trace
     float *regb_in = nullptr, *regb_out = nullptr; // pfslam_register_batch's own buffers: m x 3 starts, m x 12 result rows; they grow with m
     int regb_cap = 0, regb_cus = 0;                // rows they hold; compute units of the device (read on first use)
-    // pfslam_search's own buffers; each grows when a call needs more: the distance field, the end-point cells per (heading, beam), the
-    // in-range count per heading, the score volume (only when a caller asks for it), and key + box + result row
+    // The buffers of pfslam_search and of the entry points that share its volume runner (search_volume: pfslam_search_scan and the two cov
+    // forms); each grows when a call needs more: the distance field, the end-point cells per (heading, beam), the in-range count per
+    // heading, the score volume (when a caller or the reduction asks for it), and the one state row: key + box words + result row +
+    // point count + cov_out
     uint16_t *srch_field = nullptr;
     int2 *srch_ends = nullptr;
     int *srch_nin = nullptr, *srch_scores = nullptr;
@@ -174,15 +177,13 @@ struct pfslam_handle {
     unsigned long long *best_tab = nullptr, *best_list = nullptr, *best_state = nullptr;
     size_t best_tab_cap = 0, best_list_cap = 0;
     // pfslam_search_scan's own buffers (the field, the end points, the counts and the volume are pfslam_search's above): the reference scan
-    // and an uploaded searched scan (2 x n_beams), the reference scan's points, and key + box words + result row + point count
+    // and an uploaded searched scan (2 x n_beams), and the reference scan's points
     float *scan_in = nullptr;
     float2 *scan_pts = nullptr;
-    unsigned long long *scan_state = nullptr;
-    // pfslam_search_cov's / pfslam_search_scan_cov's own buffers (everything else is pfslam_search's and pfslam_search_scan's above): 12 tile
-    // sums per 4096-candidate tile of the volume, growing with the window, and key + box words + result row + point count + cov_out
+    // pfslam_search_cov's / pfslam_search_scan_cov's own buffer (everything else is pfslam_search's and pfslam_search_scan's above): 12 tile
+    // sums per 4096-candidate tile of the volume, growing with the window
     float *cov_part = nullptr;
     size_t cov_part_cap = 0;
-    unsigned long long *cov_state = nullptr;
     // pfslam_cast's / pfslam_map_raster's own buffers, allocated on first use and grown like pfslam_search's: the raster's 8 x 8-cell tiles,
     // the uploaded poses (m x 3), the ranges and hit cells of a call, pfslam_map_raster's bytes, and box words + counts
     unsigned long long *cast_tiles = nullptr;
@@ -1091,7 +1092,7 @@ extern "C" int pfslam_destroy(pfslam_handle *h)
                     h->fit, h->fit_i, h->partial, h->mkey, h->order2, h->cells, h->stats, h->pose, h->start, h->icp_tar, h->icp_cor, h->icp_dbg,
                     h->free_mask, h->blk_cnt, h->wall_cell, h->free_cell, h->wall_pts, h->free_pts,
                     h->wall_c, h->free_c, h->counts, h->tile_r, h->tile_r2, h->sums, h->cdf,
-                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->srch_field, h->srch_ends, h->srch_nin, h->srch_scores, h->srch_state, h->wide_field, h->wide_ends, h->wide_nin, h->wide_nodes, h->wide_lb, h->wide_state, h->best_tab, h->best_list, h->best_state, h->scan_in, h->scan_pts, h->scan_state, h->cov_part, h->cov_state, h->cast_tiles, h->cast_poses, h->cast_ranges, h->cast_cells, h->cast_state, h->cast_occ, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
+                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->srch_field, h->srch_ends, h->srch_nin, h->srch_scores, h->srch_state, h->wide_field, h->wide_ends, h->wide_nin, h->wide_nodes, h->wide_lb, h->wide_state, h->best_tab, h->best_list, h->best_state, h->scan_in, h->scan_pts, h->cov_part, h->cast_tiles, h->cast_poses, h->cast_ranges, h->cast_cells, h->cast_state, h->cast_occ, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (h->own_global) {

@@ -2,12 +2,17 @@
 // of the map); the specification is in include/pfslam.h.  Included by pfslam_hip.hip behind pfslam_register_batch.hip.inc (same
 // translation unit): it reuses pf::kd_nearest_exact, pf::clean_lidar_scan and pf::fdiv as they are.
 // tests/test_search_kernel_text.py cuts the text between the two SEARCH-KERNEL-TEXT marks out and runs it on the CPU.
+// What the search family shares on the host is here: search_derive (SearchParams from a call's arguments; inside the marks, so the CPU
+// emulators run it too), search_plan (the common refusals, in their one order, under the caller's name) and search_grow.  The one
+// volume runner, search_volume, is declared here and defined in pfslam_search_cov.hip.inc, behind the kernels of both field forms.
 
 #define PF_SEARCH_MAX_CAND (1 << 24)   /* candidates of one call: 16.8e6 candidates of 1081 beams on a 100 000-point map: 9.0 ms measured (profiles/search.txt) */
 #define PF_SEARCH_MAX_ENDS (1 << 24)   /* (2 half_theta + 1) * n_beams end points of one call: 128 MB */
-#define PF_SEARCH_MAX_FIELD (1 << 26)  /* field cells of one call: 128 MB */
+#define PF_WIDE_MAX_CAND 2147483647LL  /* candidates of one branch-and-bound call: k stays a non-negative int32, the key stays S << 32 | k */
+#define PF_WIDE_MAX_ROW (1 << 24)      /* (2 half_x + 1)(2 half_y + 1): the candidates of one heading of such a call */
 
 // SEARCH-KERNEL-TEXT-BEGIN
+#define PF_SEARCH_MAX_FIELD (1 << 26) /* field cells of one call: 128 MB */
 #define PF_SEARCH_CELL_MAX 1048576 /* 2^20: an end point farther out counts as qcap */
 #define PF_SEARCH_BIAS (1 << 21)
 #define PF_SEARCH_SKIP (-2147483647 - 1) /* ends[].y: the beam is out of range and takes no part */
@@ -22,6 +27,36 @@ struct SearchParams {
     int lox, hix, loy, hiy; // the host's bounds of the end-point cells: rint((c -+ 20) / res), inside +-2^20
     int cap;                // cells the field buffer holds: (hix - lox + 1 + 2 hx stride) * (hiy - loy + 1 + 2 hy stride), + 2 spare cells
 };
+
+// SearchParams from a call's arguments: the part of every entry point's prologue that needs neither the handle nor the device (a plain
+// host function).  *out is complete when the call fits; a refusal brings its message's figures; SEARCH_QCAP does not depend on the centre.
+enum SearchRefusal { SEARCH_FITS = 0, SEARCH_QCAP, SEARCH_FIELD };
+struct SearchWhy { float qf; long long W, H; };
+static inline SearchRefusal search_derive(float res, int nb, const float centre[3], int hx, int hy, int ht, int stride, float step_theta, float max_dist,
+                                          SearchParams *out, SearchWhy *why)
+{
+    SearchParams &p = *out;
+    p.res = res;
+    p.u = (p.res * p.res) * 0.0625f;
+    why->qf = rintf(pf::fdiv(max_dist * max_dist, p.u));
+    if (!(why->qf >= 1.0f && why->qf <= 65535.0f)) return SEARCH_QCAP;
+    p.cx = centre[0]; p.cy = centre[1]; p.ct = centre[2];
+    p.step_theta = step_theta;
+    p.hx = hx; p.hy = hy; p.ht = ht;
+    p.stride = stride;
+    p.qcap = (int)why->qf;
+    p.nb = nb;
+    auto cell_bound = [&](float c, float d) { // rint((c + d) / res) as k_search_ends computes it, inside +-2^20
+        const float f = rintf(pf::fdiv(c + d, p.res));
+        return (int)std::min(std::max(f, -(float)PF_SEARCH_CELL_MAX), (float)PF_SEARCH_CELL_MAX);
+    };
+    p.lox = cell_bound(p.cx, -PF_LIDAR_RANGE); p.hix = cell_bound(p.cx, PF_LIDAR_RANGE);
+    p.loy = cell_bound(p.cy, -PF_LIDAR_RANGE); p.hiy = cell_bound(p.cy, PF_LIDAR_RANGE);
+    const long long W = why->W = (long long)p.hix - p.lox + 1 + 2LL * p.hx * p.stride, H = why->H = (long long)p.hiy - p.loy + 1 + 2LL * p.hy * p.stride;
+    if (W > PF_SEARCH_MAX_FIELD || H > PF_SEARCH_MAX_FIELD || W * H > PF_SEARCH_MAX_FIELD) return SEARCH_FIELD;
+    p.cap = (int)(W * H);
+    return SEARCH_FITS;
+}
 
 // The field of a call is the bounding box of the end-point cells of every heading, grown by the window: its extent is known only on
 // the device, where k_search_ends merges it into four words that a memset of 0xff leaves "empty" (-1) and that only grow:
@@ -199,90 +234,73 @@ static int search_grow(T **buf, size_t *have, size_t count)
     return 0;
 }
 
+// What search_plan derives for every entry point: the kernels' parameters and the window's extent.  Then the forms of a call, or-ed.
+struct SearchPlan { SearchParams p; long long nx, ny, na; size_t cand; };
+#define PF_FORM_NO_MAP 1 /* the field comes from a reference scan: no map is needed, and a call without a centre takes ref_pose, not the handle's pose */
+#define PF_FORM_WIDE 2   /* branch and bound: up to 2^31 - 1 candidates, 2^24 of one heading */
+
+// The refusals every entry point shares, in their one order, worded under the caller's name `fn`; on success the device is current, the
+// handle settled and *out filled.  An entry point checks its own arguments before and behind this call.
+static int search_plan(pfslam_handle *h, const char *fn, int form, const float *ref_pose, const float centre[3], const pfslam_search_opts *opts, SearchPlan *out)
+{
+    const std::string name = std::string(fn) + ": ";
+    auto finite3 = [](const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); };
+    if (opts->half_x < 0 || opts->half_y < 0 || opts->half_theta < 0) return fail(name + "half_x, half_y and half_theta must be >= 0");
+    if (opts->stride < 1 || opts->stride > 64) return fail(name + "stride must be 1 .. 64");
+    if (!std::isfinite(opts->step_theta) || (opts->half_theta > 0 && !(opts->step_theta > 0.0f)))
+        return fail(name + "step_theta must be finite, and > 0 unless half_theta is 0");
+    if (!std::isfinite(opts->max_dist) || !(opts->max_dist > 0.0f)) return fail(name + "max_dist must be finite and > 0");
+    if (opts->reserved_[0] || opts->reserved_[1]) return fail(name + "reserved_ must be 0");
+    if (ref_pose && !finite3(ref_pose)) return fail(name + "the ref_pose must be finite");
+    if (centre && !finite3(centre)) return fail(name + "the centre must be finite");
+    const long long nx = 2LL * opts->half_x + 1, ny = 2LL * opts->half_y + 1, na = 2LL * opts->half_theta + 1;
+    const bool wide = (form & PF_FORM_WIDE) != 0;
+    if (wide && (nx > PF_WIDE_MAX_ROW || ny > PF_WIDE_MAX_ROW || nx * ny > PF_WIDE_MAX_ROW || nx * ny * na > PF_WIDE_MAX_CAND))
+        return fail(name + "more than 2^31 - 1 candidates, or more than 2^24 of one heading ((2 half_x + 1)(2 half_y + 1))");
+    if (!wide && (nx > PF_SEARCH_MAX_CAND || ny > PF_SEARCH_MAX_CAND || na > PF_SEARCH_MAX_CAND || nx * ny > PF_SEARCH_MAX_CAND || nx * ny * na > PF_SEARCH_MAX_CAND))
+        return fail(name + "more than 2^24 candidates");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    CHK(settle(h));
+    if (!(form & PF_FORM_NO_MAP) && h->kd_size <= 0) return fail(name + "no map loaded");
+    if (h->nb > PF_SUM_TILE) return fail(name + "n_beams > 4096 not supported");
+    if (h->cfg.map_res_x != h->cfg.map_res_y) return fail(name + "map_res_x != map_res_y not supported");
+    // the centre: given, the reference pose, or the handle's pose -- which is read only behind the two refusals that do not depend on it
+    float c3[4] = {0, 0, 0, 0};
+    const float *given = centre ? centre : ((form & PF_FORM_NO_MAP) ? ref_pose : nullptr);
+    if (given) memcpy(c3, given, 12);
+    SearchWhy why;
+    char msg[240];
+    auto derive = [&] {
+        return search_derive(h->cfg.map_res_x, h->nb, c3, opts->half_x, opts->half_y, opts->half_theta, opts->stride, opts->step_theta, opts->max_dist, &out->p, &why);
+    };
+    SearchRefusal no = derive();
+    if (no == SEARCH_QCAP) {
+        snprintf(msg, sizeof(msg), "%s: max_dist %g gives qcap %g in units of res^2 / 16; it must be 1 .. 65535", fn, (double)opts->max_dist, (double)why.qf);
+        return fail(msg);
+    }
+    if (na * h->nb > PF_SEARCH_MAX_ENDS) return fail(name + "more than 2^24 end points ((2 half_theta + 1) * n_beams)");
+    if (!given) { // as pfslam_get_pose reads it (the one case with a second copy and wait: the field's bounds need it here)
+        HIPCHK(hipMemcpyAsync(c3, h->pose, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (!finite3(c3)) return fail(name + "the centre (the handle's pose) must be finite");
+        no = derive();
+    }
+    if (no == SEARCH_FIELD) {
+        snprintf(msg, sizeof(msg), "%s: the field would have %lld x %lld cells (40 m / res + 1 + 2 half stride a side); at most 2^26 cells", fn, why.W, why.H);
+        return fail(msg);
+    }
+    out->nx = nx; out->ny = ny; out->na = na;
+    out->cand = (size_t)(nx * ny * na);
+    return 0;
+}
+
+// The one volume runner of the four windowed entry points, defined in pfslam_search_cov.hip.inc (`cov` NULL: no reduction).
+static int search_volume(pfslam_handle *h, const char *fn, int form, const float *ref_scan_host, const float ref_pose[3], const float *scan_host, const float centre[3],
+                         const pfslam_search_opts *opts, const pfslam_cov_opts *cov, float pose_out[3], float info[8], float cov_out[16], int32_t *scores);
+
 extern "C" int pfslam_search(pfslam_handle *h, const float centre[3], const pfslam_search_opts *opts, float pose_out[3], float info[8],
                              int32_t *scores)
 {
     if (!h || !opts || !pose_out || !info) return fail("pfslam_search: bad argument");
-    if (opts->half_x < 0 || opts->half_y < 0 || opts->half_theta < 0) return fail("pfslam_search: half_x, half_y and half_theta must be >= 0");
-    if (opts->stride < 1 || opts->stride > 64) return fail("pfslam_search: stride must be 1 .. 64");
-    if (!std::isfinite(opts->step_theta) || (opts->half_theta > 0 && !(opts->step_theta > 0.0f)))
-        return fail("pfslam_search: step_theta must be finite, and > 0 unless half_theta is 0");
-    if (!std::isfinite(opts->max_dist) || !(opts->max_dist > 0.0f)) return fail("pfslam_search: max_dist must be finite and > 0");
-    if (opts->reserved_[0] || opts->reserved_[1]) return fail("pfslam_search: reserved_ must be 0");
-    if (centre && !(std::isfinite(centre[0]) && std::isfinite(centre[1]) && std::isfinite(centre[2]))) return fail("pfslam_search: the centre must be finite");
-    const long long nx = 2LL * opts->half_x + 1, ny = 2LL * opts->half_y + 1, na = 2LL * opts->half_theta + 1;
-    if (nx > PF_SEARCH_MAX_CAND || ny > PF_SEARCH_MAX_CAND || na > PF_SEARCH_MAX_CAND || nx * ny > PF_SEARCH_MAX_CAND || nx * ny * na > PF_SEARCH_MAX_CAND)
-        return fail("pfslam_search: more than 2^24 candidates");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    CHK(settle(h));
-    if (h->kd_size <= 0) return fail("pfslam_search: no map loaded");
-    if (h->nb > PF_SUM_TILE) return fail("pfslam_search: n_beams > 4096 not supported");
-    if (h->cfg.map_res_x != h->cfg.map_res_y) return fail("pfslam_search: map_res_x != map_res_y not supported");
-    SearchParams p;
-    p.res = h->cfg.map_res_x;
-    p.u = (p.res * p.res) * 0.0625f;
-    const float qf = rintf(pf::fdiv(opts->max_dist * opts->max_dist, p.u));
-    if (!(qf >= 1.0f && qf <= 65535.0f)) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "pfslam_search: max_dist %g gives qcap %g in units of res^2 / 16; it must be 1 .. 65535", (double)opts->max_dist, (double)qf);
-        return fail(msg);
-    }
-    if (na * h->nb > PF_SEARCH_MAX_ENDS) return fail("pfslam_search: more than 2^24 end points ((2 half_theta + 1) * n_beams)");
-    float c3[4] = {0, 0, 0, 0};
-    if (centre) {
-        memcpy(c3, centre, 12);
-    } else { // the handle's pose, as pfslam_get_pose reads it (the one case with a second copy and wait: the field's bounds need it here)
-        HIPCHK(hipMemcpyAsync(c3, h->pose, 16, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (!(std::isfinite(c3[0]) && std::isfinite(c3[1]) && std::isfinite(c3[2]))) return fail("pfslam_search: the centre (the handle's pose) must be finite");
-    }
-    p.cx = c3[0]; p.cy = c3[1]; p.ct = c3[2];
-    p.step_theta = opts->step_theta;
-    p.hx = opts->half_x; p.hy = opts->half_y; p.ht = opts->half_theta;
-    p.stride = opts->stride;
-    p.qcap = (int)qf;
-    p.nb = h->nb;
-    auto cell_bound = [&](float c, float d) { // rint((c + d) / res) as k_search_ends computes it, inside +-2^20
-        const float f = rintf(pf::fdiv(c + d, p.res));
-        return (int)std::min(std::max(f, -(float)PF_SEARCH_CELL_MAX), (float)PF_SEARCH_CELL_MAX);
-    };
-    p.lox = cell_bound(p.cx, -PF_LIDAR_RANGE); p.hix = cell_bound(p.cx, PF_LIDAR_RANGE);
-    p.loy = cell_bound(p.cy, -PF_LIDAR_RANGE); p.hiy = cell_bound(p.cy, PF_LIDAR_RANGE);
-    const long long W = (long long)p.hix - p.lox + 1 + 2LL * p.hx * p.stride, H = (long long)p.hiy - p.loy + 1 + 2LL * p.hy * p.stride;
-    if (W > PF_SEARCH_MAX_FIELD || H > PF_SEARCH_MAX_FIELD || W * H > PF_SEARCH_MAX_FIELD) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "pfslam_search: the field would have %lld x %lld cells (40 m / res + 1 + 2 half stride a side); at most 2^26 cells", W, H);
-        return fail(msg);
-    }
-    p.cap = (int)(W * H);
-    const size_t cand = (size_t)(nx * ny * na);
-    // the feature's own device buffers; they grow when a call needs more
-    CHK(search_grow(&h->srch_field, &h->srch_field_cap, (size_t)p.cap + 2)); // (+ the two spare cells)
-    CHK(search_grow(&h->srch_ends, &h->srch_ends_cap, (size_t)na * h->nb));
-    CHK(search_grow(&h->srch_nin, &h->srch_nin_cap, (size_t)na));
-    if (scores) CHK(search_grow(&h->srch_scores, &h->srch_scores_cap, cand));
-    if (!h->srch_state) CHK(dalloc(&h->srch_state, (size_t)3 + PF_SEARCH_OUT / 2)); // key, the four box words, the result row
-    unsigned long long *key = h->srch_state;
-    int *box = (int *)(h->srch_state + 1);
-    float *out = (float *)(h->srch_state + 3);
-    HIPCHK(hipMemsetAsync(h->srch_state, 0xff, 24, h->stream));
-    hipLaunchKernelGGL(k_search_ends, dim3((unsigned)na), dim3(256), 0, h->stream, (const float *)h->scan, p, h->trig, h->srch_ends, h->srch_nin, box);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_search_field, dim3((unsigned)((p.cap + 255) / 256)), dim3(256), 0, h->stream, kd_view(h), p, (const int *)box, h->srch_field);
-    HIPCHK(hipGetLastError());
-    const int chunks = (int)((nx * ny + 63) / 64);
-    hipLaunchKernelGGL(k_search_score, dim3((unsigned)(na * chunks)), dim3(64), 0, h->stream, (const int2 *)h->srch_ends, (const int *)h->srch_nin,
-                       (const int *)box, (const uint16_t *)h->srch_field, p, chunks, scores ? h->srch_scores : nullptr, key);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_search_result, dim3(1), dim3(1), 0, h->stream, (const unsigned long long *)key, (const int *)h->srch_nin, p, out);
-    HIPCHK(hipGetLastError());
-    float r[PF_SEARCH_OUT];
-    std::vector<int32_t> sc(scores ? cand : 0); // (the caller's array is written only when the whole call has succeeded)
-    HIPCHK(hipMemcpyAsync(r, out, sizeof(r), hipMemcpyDeviceToHost, h->stream));
-    if (scores) HIPCHK(hipMemcpyAsync(sc.data(), h->srch_scores, cand * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    memcpy(pose_out, r, 12);
-    memcpy(info, r + 4, 32);
-    if (scores) memcpy(scores, sc.data(), cand * 4);
-    return 0;
+    return search_volume(h, "pfslam_search", 0, nullptr, nullptr, nullptr, centre, opts, nullptr, pose_out, info, nullptr, scores);
 }

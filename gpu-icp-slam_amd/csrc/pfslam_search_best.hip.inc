@@ -2,7 +2,8 @@
 // branch and bound with one key per cell instead of one per call); the specification is in include/pfslam.h.  Included by pfslam_hip.hip
 // behind pfslam_search_wide.hip.inc (same translation unit): k_search_ends, k_search_field, k_wide_pyramid and k_wide_top are launched as
 // they are, and the field levels, the end points, the in-range counts, the frontier and the lower bounds are pfslam_search_wide's buffers
-// (scratch that either function rewrites from the start of every call).
+// (scratch that either function rewrites from the start of every call).  The shared refusals are search_plan's (pfslam_search.hip.inc) and
+// the descent is pfslam_search_wide's wide_descend; this file brings its scoring, its threshold and expansion, and the selection behind.
 // tests/test_search_best_kernel_text.py cuts the text between the two SEARCH-BEST-KERNEL-TEXT marks out and runs it on the CPU.
 //   Measured on one MI355X, 1081 beams (profiles/search_best.txt): the whole map, 1601 x 1601 x 503 candidates in 2 545 263 cells, eight rows:
 //   15.2 ms on the 4000-point map and 19.0 ms on the 100 000-point map, 1.16 and 1.31 times pfslam_search_wide; count = 1: 1.01 and 1.02 times.
@@ -207,58 +208,10 @@ extern "C" int pfslam_search_best(pfslam_handle *h, const float centre[3], const
 {
     // pfslam_search_wide's refusals, in its order
     if (!h || !opts) return fail("pfslam_search_best: bad argument");
-    if (opts->half_x < 0 || opts->half_y < 0 || opts->half_theta < 0) return fail("pfslam_search_best: half_x, half_y and half_theta must be >= 0");
-    if (opts->stride < 1 || opts->stride > 64) return fail("pfslam_search_best: stride must be 1 .. 64");
-    if (!std::isfinite(opts->step_theta) || (opts->half_theta > 0 && !(opts->step_theta > 0.0f)))
-        return fail("pfslam_search_best: step_theta must be finite, and > 0 unless half_theta is 0");
-    if (!std::isfinite(opts->max_dist) || !(opts->max_dist > 0.0f)) return fail("pfslam_search_best: max_dist must be finite and > 0");
-    if (opts->reserved_[0] || opts->reserved_[1]) return fail("pfslam_search_best: reserved_ must be 0");
-    if (centre && !(std::isfinite(centre[0]) && std::isfinite(centre[1]) && std::isfinite(centre[2]))) return fail("pfslam_search_best: the centre must be finite");
-    const long long nx = 2LL * opts->half_x + 1, ny = 2LL * opts->half_y + 1, na = 2LL * opts->half_theta + 1;
-    if (nx > PF_WIDE_MAX_ROW || ny > PF_WIDE_MAX_ROW || nx * ny > PF_WIDE_MAX_ROW || nx * ny * na > PF_WIDE_MAX_CAND)
-        return fail("pfslam_search_best: more than 2^31 - 1 candidates, or more than 2^24 of one heading ((2 half_x + 1)(2 half_y + 1))");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    CHK(settle(h));
-    if (h->kd_size <= 0) return fail("pfslam_search_best: no map loaded");
-    if (h->nb > PF_SUM_TILE) return fail("pfslam_search_best: n_beams > 4096 not supported");
-    if (h->cfg.map_res_x != h->cfg.map_res_y) return fail("pfslam_search_best: map_res_x != map_res_y not supported");
-    SearchParams p;
-    p.res = h->cfg.map_res_x;
-    p.u = (p.res * p.res) * 0.0625f;
-    const float qf = rintf(pf::fdiv(opts->max_dist * opts->max_dist, p.u));
-    if (!(qf >= 1.0f && qf <= 65535.0f)) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "pfslam_search_best: max_dist %g gives qcap %g in units of res^2 / 16; it must be 1 .. 65535", (double)opts->max_dist, (double)qf);
-        return fail(msg);
-    }
-    if (na * h->nb > PF_SEARCH_MAX_ENDS) return fail("pfslam_search_best: more than 2^24 end points ((2 half_theta + 1) * n_beams)");
-    float c3[4] = {0, 0, 0, 0};
-    if (centre) {
-        memcpy(c3, centre, 12);
-    } else { // the handle's pose, as pfslam_get_pose reads it
-        HIPCHK(hipMemcpyAsync(c3, h->pose, 16, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (!(std::isfinite(c3[0]) && std::isfinite(c3[1]) && std::isfinite(c3[2]))) return fail("pfslam_search_best: the centre (the handle's pose) must be finite");
-    }
-    p.cx = c3[0]; p.cy = c3[1]; p.ct = c3[2];
-    p.step_theta = opts->step_theta;
-    p.hx = opts->half_x; p.hy = opts->half_y; p.ht = opts->half_theta;
-    p.stride = opts->stride;
-    p.qcap = (int)qf;
-    p.nb = h->nb;
-    auto cell_bound = [&](float c, float d) { // rint((c + d) / res) as k_search_ends computes it, inside +-2^20
-        const float f = rintf(pf::fdiv(c + d, p.res));
-        return (int)std::min(std::max(f, -(float)PF_SEARCH_CELL_MAX), (float)PF_SEARCH_CELL_MAX);
-    };
-    p.lox = cell_bound(p.cx, -PF_LIDAR_RANGE); p.hix = cell_bound(p.cx, PF_LIDAR_RANGE);
-    p.loy = cell_bound(p.cy, -PF_LIDAR_RANGE); p.hiy = cell_bound(p.cy, PF_LIDAR_RANGE);
-    const long long W = (long long)p.hix - p.lox + 1 + 2LL * p.hx * p.stride, H = (long long)p.hiy - p.loy + 1 + 2LL * p.hy * p.stride;
-    if (W > PF_SEARCH_MAX_FIELD || H > PF_SEARCH_MAX_FIELD || W * H > PF_SEARCH_MAX_FIELD) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "pfslam_search_best: the field would have %lld x %lld cells (40 m / res + 1 + 2 half stride a side); at most 2^26 cells", W, H);
-        return fail(msg);
-    }
-    p.cap = (int)(W * H);
+    SearchPlan s;
+    CHK(search_plan(h, "pfslam_search_best", PF_FORM_WIDE, nullptr, centre, opts, &s));
+    const SearchParams &p = s.p;
+    const long long nx = s.nx, ny = s.ny, na = s.na;
     // then this function's own
     if (!best || !poses_out || !info || !index || !found) return fail("pfslam_search_best: bad argument");
     if (best->count < 1 || best->count > PF_BEST_MAX_COUNT) return fail("pfslam_search_best: count must be 1 .. 64");
@@ -278,19 +231,8 @@ extern "C" int pfslam_search_best(pfslam_handle *h, const float centre[3], const
     }
     q.cells = (int)cells;
     const int want = best->count;
-    // the top level: the smallest whose one block covers a heading's window, at most PF_WIDE_MAX_LEVEL
-    int top = 0;
-    while (top < PF_WIDE_MAX_LEVEL && (1LL << top) < std::max(nx, ny)) top++;
-    const long long n_top = na * (((nx - 1) >> top) + 1) * (((ny - 1) >> top) + 1);
-    const int room = h->wide_frontier ? h->wide_frontier : PF_WIDE_FRONTIER; // nodes of one frontier buffer
-    const size_t level = (size_t)p.cap + 2;                                  // cells of one level (+ the two spare cells of k_search_field)
-    // pfslam_search_wide's scratch, and this function's own buffers: the table (representatives, then slice minima), the list (its length,
-    // then up to every cell) and threshold + box words + child count + the rows' keys + the rows; they grow when a call needs more
-    CHK(search_grow(&h->wide_field, &h->wide_field_cap, level * (size_t)(top + 1)));
-    CHK(search_grow(&h->wide_ends, &h->wide_ends_cap, (size_t)na * h->nb));
-    CHK(search_grow(&h->wide_nin, &h->wide_nin_cap, (size_t)na));
-    CHK(search_grow(&h->wide_nodes, &h->wide_nodes_cap, (size_t)room * (size_t)(top + 1)));
-    CHK(search_grow(&h->wide_lb, &h->wide_lb_cap, (size_t)room));
+    // this function's own buffers: the table (representatives, then slice minima), the list (its length, then up to every cell) and
+    // threshold + box words + child count + the rows' keys + the rows; they grow when a call needs more
     CHK(search_grow(&h->best_tab, &h->best_tab_cap, (size_t)cells + PF_BEST_SLICES));
     CHK(search_grow(&h->best_list, &h->best_list_cap, (size_t)cells + 1));
     if (!h->best_state) CHK(dalloc(&h->best_state, (size_t)PF_BEST_STATE));
@@ -301,63 +243,20 @@ extern "C" int pfslam_search_best(pfslam_handle *h, const float centre[3], const
     HIPCHK(hipMemsetAsync(h->best_state, 0xff, 24, h->stream));
     HIPCHK(hipMemsetAsync(tab, 0xff, ((size_t)cells + PF_BEST_SLICES) * 8, h->stream));
     HIPCHK(hipMemsetAsync(h->best_list, 0, 8, h->stream));
-    hipLaunchKernelGGL(k_search_ends, dim3((unsigned)na), dim3(256), 0, h->stream, (const float *)h->scan, p, h->trig, h->wide_ends, h->wide_nin, box);
-    HIPCHK(hipGetLastError());
-    const unsigned cell_blocks = (unsigned)((p.cap + 255) / 256);
-    hipLaunchKernelGGL(k_search_field, dim3(cell_blocks), dim3(256), 0, h->stream, kd_view(h), p, (const int *)box, h->wide_field);
-    HIPCHK(hipGetLastError());
-    for (int L = 1; L <= top; L++) {
-        hipLaunchKernelGGL(k_wide_pyramid, dim3(cell_blocks), dim3(256), 0, h->stream, (const int *)box, p, (1 << (L - 1)) * p.stride,
-                           (const uint16_t *)(h->wide_field + level * (size_t)(L - 1)), h->wide_field + level * (size_t)L);
-        HIPCHK(hipGetLastError());
-    }
-    // pfslam_search_wide's descent, depth first over batches of at most room / 4 nodes of one level (room at level 0); between a batch's
-    // scoring and its expansion the threshold is selected anew.  One wait per batch above level 0.
-    long long have[PF_WIDE_MAX_LEVEL + 1] = {0}, done[PF_WIDE_MAX_LEVEL + 1] = {0};
-    long long bounded = 0, scored = 0, batches = 0;
-    have[top] = n_top;
-    for (int L = top;;) {
-        if (done[L] >= have[L]) {
-            if (L == top) break;
-            L++;
-            continue;
-        }
-        const int n = (int)std::min<long long>(have[L] - done[L], L ? std::max(room / 4, 1) : room);
-        int *nodes = h->wide_nodes + (size_t)room * (size_t)L;
-        if (L == top) {
-            hipLaunchKernelGGL(k_wide_top, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, p, L, done[L], n, nodes);
-            HIPCHK(hipGetLastError());
-        } else {
-            nodes += done[L];
-        }
-        done[L] += n;
-        batches++;
-        (L ? bounded : scored) += n;
-        const uint16_t *fL = h->wide_field + level * (size_t)L;
-        if (L)
-            hipLaunchKernelGGL(k_best_score<false>, dim3((unsigned)n), dim3(64), 0, h->stream, (const int *)nodes, (const int2 *)h->wide_ends,
+    // pfslam_search_wide's descent through its scratch; between a batch's scoring and its expansion the threshold is selected anew
+    WideDescent d;
+    CHK(wide_descend(
+        h, "pfslam_search_best", s, box, count,
+        [&](auto leaf, int n, const int *nodes, const uint16_t *fL) {
+            hipLaunchKernelGGL(k_best_score<decltype(leaf)::value>, dim3((unsigned)n), dim3(64), 0, h->stream, nodes, (const int2 *)h->wide_ends,
                                (const int *)h->wide_nin, (const int *)box, (const uint16_t *)h->wide_field, fL, p, q, h->wide_lb, tab);
-        else
-            hipLaunchKernelGGL(k_best_score<true>, dim3((unsigned)n), dim3(64), 0, h->stream, (const int *)nodes, (const int2 *)h->wide_ends,
-                               (const int *)h->wide_nin, (const int *)box, (const uint16_t *)h->wide_field, fL, p, q, h->wide_lb, tab);
-        HIPCHK(hipGetLastError());
-        if (L == 0) continue;
-        HIPCHK(hipMemsetAsync(count, 0, 4, h->stream));
-        hipLaunchKernelGGL(k_best_thr, dim3(1), dim3(256), 0, h->stream, (const unsigned long long *)(tab + cells), want, thr);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_best_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const int *)nodes, (const int *)h->wide_lb, n, L, p, q,
-                           (const unsigned long long *)thr, (const unsigned long long *)tab, h->wide_nodes + (size_t)room * (size_t)(L - 1), count);
-        HIPCHK(hipGetLastError());
-        int kids = 0;
-        HIPCHK(hipMemcpyAsync(&kids, count, 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (kids < 0 || kids > 4 * n) return fail("pfslam_search_best: internal: a batch left more children than four a node");
-        if (kids) {
-            L--;
-            have[L] = kids;
-            done[L] = 0;
-        }
-    }
+        },
+        [&](int L, int n, const int *nodes, int *next) {
+            hipLaunchKernelGGL(k_best_thr, dim3(1), dim3(256), 0, h->stream, (const unsigned long long *)(tab + cells), want, thr);
+            hipLaunchKernelGGL(k_best_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nodes, (const int *)h->wide_lb, n, L, p, q,
+                               (const unsigned long long *)thr, (const unsigned long long *)tab, next, count);
+        },
+        &d));
     // The selection: the last threshold, the cells at or below it (at least `count` of them, or every cell that has a representative),
     // their exact order on the host.  The first copy takes the list's head, which is the whole list unless many cells share a slice.
     hipLaunchKernelGGL(k_best_thr, dim3(1), dim3(256), 0, h->stream, (const unsigned long long *)(tab + cells), want, thr);
@@ -395,16 +294,8 @@ extern "C" int pfslam_search_best(pfslam_handle *h, const float centre[3], const
     }
     *found = n_rows;
     if (stats) {
-        // the box as search_box computes it: empty when no beam of any heading has a cell
-        const long long box_cells = bw[0] < 0 ? 0 : ((long long)bw[1] + bw[0] - 2LL * PF_SEARCH_BIAS + 1 + 2LL * p.hx * p.stride) *
-                                                        ((long long)bw[3] + bw[2] - 2LL * PF_SEARCH_BIAS + 1 + 2LL * p.hy * p.stride);
         stats[0] = n_rows ? (int64_t)(list[1] & 0xffffffffull) : -1;
-        stats[1] = nx * ny * na;
-        stats[2] = bounded;
-        stats[3] = scored;
-        stats[4] = top;
-        stats[5] = batches;
-        stats[6] = box_cells;
+        wide_stats(s, d, bw, stats);
         stats[7] = cells;
     }
     return 0;

@@ -4,6 +4,7 @@
 // translation unit): the volume comes from k_search_ends, k_search_field / the scan splat, k_search_score and k_search_result as they
 // are, the sums from pfslam_estimate's device functions (est_moments, est_means, est_centred, est_finish, wave_sum_canonical) as they
 // are.  What is new is how a tile of 4096 candidates gets into LDS: a score becomes a weight (pf::exp2m), an index becomes a pose.
+// Behind the kernels stands search_volume, the one volume runner of pfslam_search, pfslam_search_scan and this file's two entry points.
 // tests/test_search_cov_kernel_text.py cuts the text between the two SEARCH-COV-KERNEL-TEXT marks out and runs it on the CPU.
 
 // SEARCH-COV-KERNEL-TEXT-BEGIN
@@ -159,113 +160,62 @@ static CovStep cov_step_of(long long n, long long nx, long long ny)
     return CovStep{(int)(n % nx), (int)(t % ny), (int)(t / ny)};
 }
 
-// Both entry points: pfslam_search's (scan_form: pfslam_search_scan's) checks in their order and wording under the name `fn`, the same
-// launches into the same buffers, then the reduction.  Key, box words, result row, point count and cov_out are this file's own row.
-static int search_cov_run(pfslam_handle *h, const char *fn, bool scan_form, const float *ref_scan_host, const float ref_pose[3],
-                          const float *scan_host, const float centre[3], const pfslam_search_opts *opts, const pfslam_cov_opts *cov,
-                          float pose_out[3], float info[8], float cov_out[16], int32_t *scores)
+// The family's one volume runner (declared in pfslam_search.hip.inc): search_plan, then end points, field (the map's tree, or under
+// PF_FORM_NO_MAP the points of ref_scan_host), scores and result into the srch_* buffers, with `cov` the reduction, one copy, one wait, and
+// the caller's arrays only on success.  The state row srch_state serves all four entry points: key, the four box words, then one row of
+// floats -- the result row, the point count (scan forms), three spare words, cov_out.  Every call memsets it, runs on the handle's stream
+// and waits before it returns, so no call reads what another left.
+#define PF_SEARCH_ROW (PF_SEARCH_OUT + 4 + PF_COV_OUT)
+static int search_volume(pfslam_handle *h, const char *fn, int form, const float *ref_scan_host, const float ref_pose[3], const float *scan_host, const float centre[3],
+                         const pfslam_search_opts *opts, const pfslam_cov_opts *cov, float pose_out[3], float info[8], float cov_out[16], int32_t *scores)
 {
     const std::string name = std::string(fn) + ": ";
-    if (!h || !opts || !pose_out || !info || !cov || !cov_out) return fail(name + "bad argument");
-    if (scan_form && !ref_scan_host) return fail(name + "ref_scan_host must not be NULL");
-    if (opts->half_x < 0 || opts->half_y < 0 || opts->half_theta < 0) return fail(name + "half_x, half_y and half_theta must be >= 0");
-    if (opts->stride < 1 || opts->stride > 64) return fail(name + "stride must be 1 .. 64");
-    if (!std::isfinite(opts->step_theta) || (opts->half_theta > 0 && !(opts->step_theta > 0.0f)))
-        return fail(name + "step_theta must be finite, and > 0 unless half_theta is 0");
-    if (!std::isfinite(opts->max_dist) || !(opts->max_dist > 0.0f)) return fail(name + "max_dist must be finite and > 0");
-    if (opts->reserved_[0] || opts->reserved_[1]) return fail(name + "reserved_ must be 0");
-    if (scan_form && ref_pose && !(std::isfinite(ref_pose[0]) && std::isfinite(ref_pose[1]) && std::isfinite(ref_pose[2])))
-        return fail(name + "the ref_pose must be finite");
-    if (centre && !(std::isfinite(centre[0]) && std::isfinite(centre[1]) && std::isfinite(centre[2]))) return fail(name + "the centre must be finite");
-    const long long nx = 2LL * opts->half_x + 1, ny = 2LL * opts->half_y + 1, na = 2LL * opts->half_theta + 1;
-    if (nx > PF_SEARCH_MAX_CAND || ny > PF_SEARCH_MAX_CAND || na > PF_SEARCH_MAX_CAND || nx * ny > PF_SEARCH_MAX_CAND || nx * ny * na > PF_SEARCH_MAX_CAND)
-        return fail(name + "more than 2^24 candidates");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    CHK(settle(h));
-    if (!scan_form && h->kd_size <= 0) return fail(name + "no map loaded");
-    if (h->nb > PF_SUM_TILE) return fail(name + "n_beams > 4096 not supported");
-    if (h->cfg.map_res_x != h->cfg.map_res_y) return fail(name + "map_res_x != map_res_y not supported");
-    SearchParams p;
-    p.res = h->cfg.map_res_x;
-    p.u = (p.res * p.res) * 0.0625f;
-    const float qf = rintf(pf::fdiv(opts->max_dist * opts->max_dist, p.u));
-    if (!(qf >= 1.0f && qf <= 65535.0f)) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "%s: max_dist %g gives qcap %g in units of res^2 / 16; it must be 1 .. 65535", fn, (double)opts->max_dist, (double)qf);
-        return fail(msg);
-    }
-    if (na * h->nb > PF_SEARCH_MAX_ENDS) return fail(name + "more than 2^24 end points ((2 half_theta + 1) * n_beams)");
+    const bool scan_form = (form & PF_FORM_NO_MAP) != 0;
     const float zero[3] = {0.0f, 0.0f, 0.0f};
-    const float *rp = ref_pose ? ref_pose : zero;
-    float c3[4] = {0, 0, 0, 0};
-    if (scan_form) {
-        memcpy(c3, centre ? centre : rp, 12);
-    } else if (centre) {
-        memcpy(c3, centre, 12);
-    } else { // the handle's pose, as pfslam_search reads it
-        HIPCHK(hipMemcpyAsync(c3, h->pose, 16, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (!(std::isfinite(c3[0]) && std::isfinite(c3[1]) && std::isfinite(c3[2]))) return fail(name + "the centre (the handle's pose) must be finite");
-    }
-    p.cx = c3[0]; p.cy = c3[1]; p.ct = c3[2];
-    p.step_theta = opts->step_theta;
-    p.hx = opts->half_x; p.hy = opts->half_y; p.ht = opts->half_theta;
-    p.stride = opts->stride;
-    p.qcap = (int)qf;
-    p.nb = h->nb;
-    auto cell_bound = [&](float c, float d) { // rint((c + d) / res) as k_search_ends computes it, inside +-2^20
-        const float f = rintf(pf::fdiv(c + d, p.res));
-        return (int)std::min(std::max(f, -(float)PF_SEARCH_CELL_MAX), (float)PF_SEARCH_CELL_MAX);
-    };
-    p.lox = cell_bound(p.cx, -PF_LIDAR_RANGE); p.hix = cell_bound(p.cx, PF_LIDAR_RANGE);
-    p.loy = cell_bound(p.cy, -PF_LIDAR_RANGE); p.hiy = cell_bound(p.cy, PF_LIDAR_RANGE);
-    const long long W = (long long)p.hix - p.lox + 1 + 2LL * p.hx * p.stride, H = (long long)p.hiy - p.loy + 1 + 2LL * p.hy * p.stride;
-    if (W > PF_SEARCH_MAX_FIELD || H > PF_SEARCH_MAX_FIELD || W * H > PF_SEARCH_MAX_FIELD) {
-        char msg[240];
-        snprintf(msg, sizeof(msg), "%s: the field would have %lld x %lld cells (40 m / res + 1 + 2 half stride a side); at most 2^26 cells", fn, W, H);
-        return fail(msg);
-    }
-    p.cap = (int)(W * H);
-    // behind the search's own checks, before any launch: the options of the covariance
-    if (!std::isfinite(cov->sigma) || !(cov->sigma > 0.0f)) return fail(name + "sigma must be finite and > 0");
-    if (cov->reserved_[0] || cov->reserved_[1] || cov->reserved_[2]) return fail(name + "the reserved_ of pfslam_cov_opts must be 0");
+    const float *rp = scan_form ? (ref_pose ? ref_pose : zero) : nullptr;
+    SearchPlan s;
+    CHK(search_plan(h, fn, form, rp, centre, opts, &s));
+    const SearchParams &p = s.p;
+    const size_t cand = s.cand;
     CovParams q;
-    q.hs = pf::fdiv(p.u * 1.442695f, (2.0f * cov->sigma) * cov->sigma);
-    if (!std::isfinite(q.hs) || !(q.hs > 0.0f)) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "%s: sigma %g gives the scale hs = %g; it must be finite and > 0", fn, (double)cov->sigma, (double)q.hs);
-        return fail(msg);
+    int nt = 0;
+    if (cov) { // behind the search's own checks, before any launch: the options of the covariance
+        if (!std::isfinite(cov->sigma) || !(cov->sigma > 0.0f)) return fail(name + "sigma must be finite and > 0");
+        if (cov->reserved_[0] || cov->reserved_[1] || cov->reserved_[2]) return fail(name + "the reserved_ of pfslam_cov_opts must be 0");
+        q.hs = pf::fdiv(p.u * 1.442695f, (2.0f * cov->sigma) * cov->sigma);
+        if (!std::isfinite(q.hs) || !(q.hs > 0.0f)) {
+            char msg[200];
+            snprintf(msg, sizeof(msg), "%s: sigma %g gives the scale hs = %g; it must be finite and > 0", fn, (double)cov->sigma, (double)q.hs);
+            return fail(msg);
+        }
+        q.cand = (int)cand;
+        q.wg = cov_step_of(PF_EST_WAVES * 64, s.nx, s.ny);
+        q.wave = cov_step_of(64, s.nx, s.ny);
+        nt = (int)((cand + PF_SUM_TILE - 1) / PF_SUM_TILE); // <= 4096: the tile sums fit one tile
     }
-    const size_t cand = (size_t)(nx * ny * na);
-    q.cand = (int)cand;
-    q.wg = cov_step_of(PF_EST_WAVES * 64, nx, ny);
-    q.wave = cov_step_of(64, nx, ny);
-    const int nt = (int)((cand + PF_SUM_TILE - 1) / PF_SUM_TILE); // <= 4096: the tile sums fit one tile
-    // pfslam_search's field, end points, counts and volume (every call rebuilds them; the volume is always built here);
-    // pfslam_search_scan's scans and points; the tile sums and the state row are this file's own
+    // the feature's own device buffers; they grow when a call needs more.  The volume is built when the caller asks for it, and always
+    // for the reduction; the scans and the points are the scan forms', the tile sums the reduction's
+    const bool volume = scores || cov;
     CHK(search_grow(&h->srch_field, &h->srch_field_cap, (size_t)p.cap + 2)); // (+ the two spare cells)
-    CHK(search_grow(&h->srch_ends, &h->srch_ends_cap, (size_t)na * h->nb));
-    CHK(search_grow(&h->srch_nin, &h->srch_nin_cap, (size_t)na));
-    CHK(search_grow(&h->srch_scores, &h->srch_scores_cap, cand));
-    CHK(search_grow(&h->cov_part, &h->cov_part_cap, (size_t)12 * nt));
-    if (scan_form) {
-        if (!h->scan_in) CHK(dalloc(&h->scan_in, (size_t)2 * h->nb));
-        if (!h->scan_pts) CHK(dalloc(&h->scan_pts, (size_t)h->nb));
-    }
-    // key, the four box words, then one row of floats: the result row, the point count, three spare words, cov_out
-    const int row_floats = PF_SEARCH_OUT + 4 + PF_COV_OUT;
-    if (!h->cov_state) CHK(dalloc(&h->cov_state, (size_t)3 + row_floats / 2));
-    unsigned long long *key = h->cov_state;
-    int *box = (int *)(h->cov_state + 1);
-    float *out = (float *)(h->cov_state + 3);
+    CHK(search_grow(&h->srch_ends, &h->srch_ends_cap, (size_t)s.na * h->nb));
+    CHK(search_grow(&h->srch_nin, &h->srch_nin_cap, (size_t)s.na));
+    if (volume) CHK(search_grow(&h->srch_scores, &h->srch_scores_cap, cand));
+    if (cov) CHK(search_grow(&h->cov_part, &h->cov_part_cap, (size_t)12 * nt));
+    if (scan_form && !h->scan_in) CHK(dalloc(&h->scan_in, (size_t)2 * h->nb));
+    if (scan_form && !h->scan_pts) CHK(dalloc(&h->scan_pts, (size_t)h->nb));
+    if (!h->srch_state) CHK(dalloc(&h->srch_state, (size_t)3 + PF_SEARCH_ROW / 2));
+    unsigned long long *key = h->srch_state;
+    int *box = (int *)(h->srch_state + 1);
+    float *out = (float *)(h->srch_state + 3);
     int *count = (int *)(out + PF_SEARCH_OUT);
     float *dcov = out + PF_SEARCH_OUT + 4;
-    HIPCHK(hipMemsetAsync(h->cov_state, 0xff, 24, h->stream));
-    if (scan_form) {
+    int *vol = volume ? h->srch_scores : nullptr;
+    HIPCHK(hipMemsetAsync(h->srch_state, 0xff, 24, h->stream));
+    const float *scan = h->scan;
+    if (scan_form) { // the reference scan's points, before the end points as ever
         HIPCHK(hipMemsetAsync(count, 0, 4, h->stream));
         // (the callers' arrays are pageable: they are consumed before the call returns, behind its one wait)
         HIPCHK(hipMemcpyAsync(h->scan_in, ref_scan_host, (size_t)h->nb * 4, hipMemcpyHostToDevice, h->stream));
-        const float *scan = h->scan;
         if (scan_host) {
             HIPCHK(hipMemcpyAsync(h->scan_in + h->nb, scan_host, (size_t)h->nb * 4, hipMemcpyHostToDevice, h->stream));
             scan = h->scan_in + h->nb;
@@ -273,34 +223,35 @@ static int search_cov_run(pfslam_handle *h, const char *fn, bool scan_form, cons
         hipLaunchKernelGGL(k_scan_points, dim3((unsigned)((h->nb + 255) / 256)), dim3(256), 0, h->stream, (const float *)h->scan_in, rp[0], rp[1], rp[2],
                            h->nb, h->trig, h->scan_pts, count);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_search_ends, dim3((unsigned)na), dim3(256), 0, h->stream, scan, p, h->trig, h->srch_ends, h->srch_nin, box);
-        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_search_ends, dim3((unsigned)s.na), dim3(256), 0, h->stream, scan, p, h->trig, h->srch_ends, h->srch_nin, box);
+    HIPCHK(hipGetLastError());
+    if (scan_form) {
         CHK(scan_field_from_points(h, h->scan_pts, h->nb, p, opts->max_dist, box, h->srch_field));
     } else {
-        hipLaunchKernelGGL(k_search_ends, dim3((unsigned)na), dim3(256), 0, h->stream, (const float *)h->scan, p, h->trig, h->srch_ends, h->srch_nin, box);
-        HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_search_field, dim3((unsigned)((p.cap + 255) / 256)), dim3(256), 0, h->stream, kd_view(h), p, (const int *)box, h->srch_field);
         HIPCHK(hipGetLastError());
     }
-    const int chunks = (int)((nx * ny + 63) / 64);
-    hipLaunchKernelGGL(k_search_score, dim3((unsigned)(na * chunks)), dim3(64), 0, h->stream, (const int2 *)h->srch_ends, (const int *)h->srch_nin,
-                       (const int *)box, (const uint16_t *)h->srch_field, p, chunks, h->srch_scores, key);
+    const int chunks = (int)((s.nx * s.ny + 63) / 64);
+    hipLaunchKernelGGL(k_search_score, dim3((unsigned)(s.na * chunks)), dim3(64), 0, h->stream, (const int2 *)h->srch_ends, (const int *)h->srch_nin,
+                       (const int *)box, (const uint16_t *)h->srch_field, p, chunks, vol, key);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_search_result, dim3(1), dim3(1), 0, h->stream, (const unsigned long long *)key, (const int *)h->srch_nin, p, out);
     HIPCHK(hipGetLastError());
-    // the reduction over the volume: moments, centred moments, the final sums (one workgroup does all three up to one tile)
-    const dim3 wg(PF_EST_WAVES * 64);
-    float *part = h->cov_part;
-    if (nt == 1) {
-        hipLaunchKernelGGL(k_cov_small, dim3(1), wg, 0, h->stream, (const int *)h->srch_scores, (const unsigned long long *)key, p, q, part, dcov);
-    } else {
-        hipLaunchKernelGGL(k_cov_moments, dim3(nt), wg, 0, h->stream, (const int *)h->srch_scores, (const unsigned long long *)key, p, q, part, nt);
-        hipLaunchKernelGGL(k_cov_centred, dim3(nt), wg, 0, h->stream, (const int *)h->srch_scores, (const unsigned long long *)key, p, q,
-                           (const float *)part, part + (size_t)5 * nt, nt);
-        hipLaunchKernelGGL(k_cov_final, dim3(1), dim3(64), 0, h->stream, (const float *)part, (const unsigned long long *)key, q, nt, dcov);
+    if (cov) { // the reduction over the volume: moments, centred moments, the final sums (one workgroup does all three up to one tile)
+        const dim3 wg(PF_EST_WAVES * 64);
+        float *part = h->cov_part;
+        if (nt == 1) {
+            hipLaunchKernelGGL(k_cov_small, dim3(1), wg, 0, h->stream, (const int *)vol, (const unsigned long long *)key, p, q, part, dcov);
+        } else {
+            hipLaunchKernelGGL(k_cov_moments, dim3(nt), wg, 0, h->stream, (const int *)vol, (const unsigned long long *)key, p, q, part, nt);
+            hipLaunchKernelGGL(k_cov_centred, dim3(nt), wg, 0, h->stream, (const int *)vol, (const unsigned long long *)key, p, q,
+                               (const float *)part, part + (size_t)5 * nt, nt);
+            hipLaunchKernelGGL(k_cov_final, dim3(1), dim3(64), 0, h->stream, (const float *)part, (const unsigned long long *)key, q, nt, dcov);
+        }
+        HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipGetLastError());
-    float r[PF_SEARCH_OUT + 4 + PF_COV_OUT];
+    float r[PF_SEARCH_ROW];
     std::vector<int32_t> sc(scores ? cand : 0); // (the caller's array is written only when the whole call has succeeded)
     HIPCHK(hipMemcpyAsync(r, out, sizeof(r), hipMemcpyDeviceToHost, h->stream));
     if (scores) HIPCHK(hipMemcpyAsync(sc.data(), h->srch_scores, cand * 4, hipMemcpyDeviceToHost, h->stream));
@@ -312,7 +263,7 @@ static int search_cov_run(pfslam_handle *h, const char *fn, bool scan_form, cons
     }
     memcpy(pose_out, r, 12);
     memcpy(info, r + 4, 32);
-    memcpy(cov_out, r + PF_SEARCH_OUT + 4, PF_COV_OUT * 4);
+    if (cov) memcpy(cov_out, r + PF_SEARCH_OUT + 4, PF_COV_OUT * 4);
     if (scores) memcpy(scores, sc.data(), cand * 4);
     return 0;
 }
@@ -320,12 +271,15 @@ static int search_cov_run(pfslam_handle *h, const char *fn, bool scan_form, cons
 extern "C" int pfslam_search_cov(pfslam_handle *h, const float centre[3], const pfslam_search_opts *opts, const pfslam_cov_opts *cov,
                                  float pose_out[3], float info[8], float cov_out[16], int32_t *scores)
 {
-    return search_cov_run(h, "pfslam_search_cov", false, nullptr, nullptr, nullptr, centre, opts, cov, pose_out, info, cov_out, scores);
+    if (!h || !opts || !pose_out || !info || !cov || !cov_out) return fail("pfslam_search_cov: bad argument");
+    return search_volume(h, "pfslam_search_cov", 0, nullptr, nullptr, nullptr, centre, opts, cov, pose_out, info, cov_out, scores);
 }
 
 extern "C" int pfslam_search_scan_cov(pfslam_handle *h, const float *ref_scan_host, const float ref_pose[3], const float *scan_host,
                                       const float centre[3], const pfslam_search_opts *opts, const pfslam_cov_opts *cov, float pose_out[3],
                                       float info[8], float cov_out[16], int32_t *scores)
 {
-    return search_cov_run(h, "pfslam_search_scan_cov", true, ref_scan_host, ref_pose, scan_host, centre, opts, cov, pose_out, info, cov_out, scores);
+    if (!h || !opts || !pose_out || !info || !cov || !cov_out) return fail("pfslam_search_scan_cov: bad argument");
+    if (!ref_scan_host) return fail("pfslam_search_scan_cov: ref_scan_host must not be NULL");
+    return search_volume(h, "pfslam_search_scan_cov", PF_FORM_NO_MAP, ref_scan_host, ref_pose, scan_host, centre, opts, cov, pose_out, info, cov_out, scores);
 }

@@ -1,7 +1,8 @@
 // pfslam_search_scan.hip.inc -- pfslam_search_scan (correlative scan-to-scan search: pfslam_search's window scored against a distance field
 // built from the end points of a reference scan instead of the map; the handle needs no map); the specification is in include/pfslam.h.
 // Included by pfslam_hip.hip behind pfslam_search.hip.inc (same translation unit): it reuses SearchParams, search_box, k_search_ends,
-// k_search_score, k_search_result and search_grow as they are, and leaves the field in the layout k_search_score reads.
+// k_search_score and k_search_result as they are, and leaves the field in the layout k_search_score reads.  The entry point is a thin
+// call into the family's one volume runner, search_volume (pfslam_search_cov.hip.inc), which launches this file's kernels for the field.
 // tests/test_search_scan_kernel_text.py cuts the text between the two SEARCH-SCAN-KERNEL-TEXT marks out and runs it on the CPU.
 
 // SEARCH-SCAN-KERNEL-TEXT-BEGIN
@@ -121,97 +122,5 @@ extern "C" int pfslam_search_scan(pfslam_handle *h, const float *ref_scan_host, 
 {
     if (!h || !opts || !pose_out || !info) return fail("pfslam_search_scan: bad argument");
     if (!ref_scan_host) return fail("pfslam_search_scan: ref_scan_host must not be NULL");
-    if (opts->half_x < 0 || opts->half_y < 0 || opts->half_theta < 0) return fail("pfslam_search_scan: half_x, half_y and half_theta must be >= 0");
-    if (opts->stride < 1 || opts->stride > 64) return fail("pfslam_search_scan: stride must be 1 .. 64");
-    if (!std::isfinite(opts->step_theta) || (opts->half_theta > 0 && !(opts->step_theta > 0.0f)))
-        return fail("pfslam_search_scan: step_theta must be finite, and > 0 unless half_theta is 0");
-    if (!std::isfinite(opts->max_dist) || !(opts->max_dist > 0.0f)) return fail("pfslam_search_scan: max_dist must be finite and > 0");
-    if (opts->reserved_[0] || opts->reserved_[1]) return fail("pfslam_search_scan: reserved_ must be 0");
-    if (ref_pose && !(std::isfinite(ref_pose[0]) && std::isfinite(ref_pose[1]) && std::isfinite(ref_pose[2]))) return fail("pfslam_search_scan: the ref_pose must be finite");
-    if (centre && !(std::isfinite(centre[0]) && std::isfinite(centre[1]) && std::isfinite(centre[2]))) return fail("pfslam_search_scan: the centre must be finite");
-    const long long nx = 2LL * opts->half_x + 1, ny = 2LL * opts->half_y + 1, na = 2LL * opts->half_theta + 1;
-    if (nx > PF_SEARCH_MAX_CAND || ny > PF_SEARCH_MAX_CAND || na > PF_SEARCH_MAX_CAND || nx * ny > PF_SEARCH_MAX_CAND || nx * ny * na > PF_SEARCH_MAX_CAND)
-        return fail("pfslam_search_scan: more than 2^24 candidates");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    CHK(settle(h));
-    if (h->nb > PF_SUM_TILE) return fail("pfslam_search_scan: n_beams > 4096 not supported");
-    if (h->cfg.map_res_x != h->cfg.map_res_y) return fail("pfslam_search_scan: map_res_x != map_res_y not supported");
-    SearchParams p;
-    p.res = h->cfg.map_res_x;
-    p.u = (p.res * p.res) * 0.0625f;
-    const float qf = rintf(pf::fdiv(opts->max_dist * opts->max_dist, p.u));
-    if (!(qf >= 1.0f && qf <= 65535.0f)) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "pfslam_search_scan: max_dist %g gives qcap %g in units of res^2 / 16; it must be 1 .. 65535", (double)opts->max_dist, (double)qf);
-        return fail(msg);
-    }
-    if (na * h->nb > PF_SEARCH_MAX_ENDS) return fail("pfslam_search_scan: more than 2^24 end points ((2 half_theta + 1) * n_beams)");
-    const float zero[3] = {0.0f, 0.0f, 0.0f};
-    const float *rp = ref_pose ? ref_pose : zero, *c3 = centre ? centre : rp;
-    p.cx = c3[0]; p.cy = c3[1]; p.ct = c3[2];
-    p.step_theta = opts->step_theta;
-    p.hx = opts->half_x; p.hy = opts->half_y; p.ht = opts->half_theta;
-    p.stride = opts->stride;
-    p.qcap = (int)qf;
-    p.nb = h->nb;
-    auto cell_bound = [&](float c, float d) { // rint((c + d) / res) as k_search_ends computes it, inside +-2^20
-        const float f = rintf(pf::fdiv(c + d, p.res));
-        return (int)std::min(std::max(f, -(float)PF_SEARCH_CELL_MAX), (float)PF_SEARCH_CELL_MAX);
-    };
-    p.lox = cell_bound(p.cx, -PF_LIDAR_RANGE); p.hix = cell_bound(p.cx, PF_LIDAR_RANGE);
-    p.loy = cell_bound(p.cy, -PF_LIDAR_RANGE); p.hiy = cell_bound(p.cy, PF_LIDAR_RANGE);
-    const long long W = (long long)p.hix - p.lox + 1 + 2LL * p.hx * p.stride, H = (long long)p.hiy - p.loy + 1 + 2LL * p.hy * p.stride;
-    if (W > PF_SEARCH_MAX_FIELD || H > PF_SEARCH_MAX_FIELD || W * H > PF_SEARCH_MAX_FIELD) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "pfslam_search_scan: the field would have %lld x %lld cells (40 m / res + 1 + 2 half stride a side); at most 2^26 cells", W, H);
-        return fail(msg);
-    }
-    p.cap = (int)(W * H);
-    const size_t cand = (size_t)(nx * ny * na);
-    // pfslam_search's field, end points, counts and volume serve this call too (every call of either rebuilds them); the two scans, the
-    // points and key + box + result row + point count are this entry's own, so that nothing another entry point reads is written
-    CHK(search_grow(&h->srch_field, &h->srch_field_cap, (size_t)p.cap + 2)); // (+ the two spare cells)
-    CHK(search_grow(&h->srch_ends, &h->srch_ends_cap, (size_t)na * h->nb));
-    CHK(search_grow(&h->srch_nin, &h->srch_nin_cap, (size_t)na));
-    if (scores) CHK(search_grow(&h->srch_scores, &h->srch_scores_cap, cand));
-    if (!h->scan_in) CHK(dalloc(&h->scan_in, (size_t)2 * h->nb));
-    if (!h->scan_pts) CHK(dalloc(&h->scan_pts, (size_t)h->nb));
-    if (!h->scan_state) CHK(dalloc(&h->scan_state, (size_t)3 + PF_SEARCH_OUT / 2 + 1)); // key, the four box words, the result row, the point count
-    unsigned long long *key = h->scan_state;
-    int *box = (int *)(h->scan_state + 1);
-    float *out = (float *)(h->scan_state + 3);
-    int *count = (int *)(out + PF_SEARCH_OUT);
-    HIPCHK(hipMemsetAsync(h->scan_state, 0xff, 24, h->stream));
-    HIPCHK(hipMemsetAsync(count, 0, 4, h->stream));
-    // (the callers' arrays are pageable: they are consumed before the call returns, behind its one wait)
-    HIPCHK(hipMemcpyAsync(h->scan_in, ref_scan_host, (size_t)h->nb * 4, hipMemcpyHostToDevice, h->stream));
-    const float *scan = h->scan;
-    if (scan_host) {
-        HIPCHK(hipMemcpyAsync(h->scan_in + h->nb, scan_host, (size_t)h->nb * 4, hipMemcpyHostToDevice, h->stream));
-        scan = h->scan_in + h->nb;
-    }
-    hipLaunchKernelGGL(k_scan_points, dim3((unsigned)((h->nb + 255) / 256)), dim3(256), 0, h->stream, (const float *)h->scan_in, rp[0], rp[1], rp[2], h->nb,
-                       h->trig, h->scan_pts, count);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_search_ends, dim3((unsigned)na), dim3(256), 0, h->stream, scan, p, h->trig, h->srch_ends, h->srch_nin, box);
-    HIPCHK(hipGetLastError());
-    CHK(scan_field_from_points(h, h->scan_pts, h->nb, p, opts->max_dist, box, h->srch_field));
-    const int chunks = (int)((nx * ny + 63) / 64);
-    hipLaunchKernelGGL(k_search_score, dim3((unsigned)(na * chunks)), dim3(64), 0, h->stream, (const int2 *)h->srch_ends, (const int *)h->srch_nin,
-                       (const int *)box, (const uint16_t *)h->srch_field, p, chunks, scores ? h->srch_scores : nullptr, key);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_search_result, dim3(1), dim3(1), 0, h->stream, (const unsigned long long *)key, (const int *)h->srch_nin, p, out);
-    HIPCHK(hipGetLastError());
-    float r[PF_SEARCH_OUT + 1];
-    std::vector<int32_t> sc(scores ? cand : 0); // (the caller's array is written only when the whole call has succeeded)
-    HIPCHK(hipMemcpyAsync(r, out, sizeof(r), hipMemcpyDeviceToHost, h->stream));
-    if (scores) HIPCHK(hipMemcpyAsync(sc.data(), h->srch_scores, cand * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    int npts;
-    memcpy(&npts, r + PF_SEARCH_OUT, 4);
-    r[4 + 7] = (float)npts;
-    memcpy(pose_out, r, 12);
-    memcpy(info, r + 4, 32);
-    if (scores) memcpy(scores, sc.data(), cand * 4);
-    return 0;
+    return search_volume(h, "pfslam_search_scan", PF_FORM_NO_MAP, ref_scan_host, ref_pose, scan_host, centre, opts, nullptr, pose_out, info, nullptr, scores);
 }

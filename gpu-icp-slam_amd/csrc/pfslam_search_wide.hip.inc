@@ -2,9 +2,9 @@
 // bound over min-pooled copies of the field); the specification is in include/pfslam.h.  Included by pfslam_hip.hip behind
 // pfslam_search.hip.inc (same translation unit): k_search_ends, k_search_field and k_search_result are launched as they are.
 // tests/test_search_wide_kernel_text.py cuts the text between the two SEARCH-WIDE-KERNEL-TEXT marks out and runs it on the CPU.
+// The refusals are search_plan's (pfslam_search.hip.inc; the candidate limits PF_WIDE_MAX_CAND and PF_WIDE_MAX_ROW stand there too).  The
+// descent, wide_descend, is here once for this entry point and for pfslam_search_best, which bring their own scoring and expansion.
 
-#define PF_WIDE_MAX_CAND 2147483647LL /* candidates of one call: k stays a non-negative int32, the key stays S << 32 | k */
-#define PF_WIDE_MAX_ROW (1 << 24)     /* (2 half_x + 1)(2 half_y + 1): the candidates of one heading */
 #define PF_WIDE_FRONTIER (1 << 22)    /* nodes a frontier buffer holds unless pfslam_debug_search_frontier says otherwise: 16 MB a level */
 
 // SEARCH-WIDE-KERNEL-TEXT-BEGIN
@@ -144,81 +144,45 @@ extern "C" int pfslam_debug_search_frontier(pfslam_handle *h, int nodes)
     return 0;
 }
 
-extern "C" int pfslam_search_wide(pfslam_handle *h, const float centre[3], const pfslam_search_opts *opts, float pose_out[3], float info[8],
-                                  int64_t stats[8])
+static long long search_box_cells(const int bw[4], const SearchParams &p)
 {
-    if (!h || !opts || !pose_out || !info) return fail("pfslam_search_wide: bad argument");
-    if (opts->half_x < 0 || opts->half_y < 0 || opts->half_theta < 0) return fail("pfslam_search_wide: half_x, half_y and half_theta must be >= 0");
-    if (opts->stride < 1 || opts->stride > 64) return fail("pfslam_search_wide: stride must be 1 .. 64");
-    if (!std::isfinite(opts->step_theta) || (opts->half_theta > 0 && !(opts->step_theta > 0.0f)))
-        return fail("pfslam_search_wide: step_theta must be finite, and > 0 unless half_theta is 0");
-    if (!std::isfinite(opts->max_dist) || !(opts->max_dist > 0.0f)) return fail("pfslam_search_wide: max_dist must be finite and > 0");
-    if (opts->reserved_[0] || opts->reserved_[1]) return fail("pfslam_search_wide: reserved_ must be 0");
-    if (centre && !(std::isfinite(centre[0]) && std::isfinite(centre[1]) && std::isfinite(centre[2]))) return fail("pfslam_search_wide: the centre must be finite");
-    const long long nx = 2LL * opts->half_x + 1, ny = 2LL * opts->half_y + 1, na = 2LL * opts->half_theta + 1;
-    if (nx > PF_WIDE_MAX_ROW || ny > PF_WIDE_MAX_ROW || nx * ny > PF_WIDE_MAX_ROW || nx * ny * na > PF_WIDE_MAX_CAND)
-        return fail("pfslam_search_wide: more than 2^31 - 1 candidates, or more than 2^24 of one heading ((2 half_x + 1)(2 half_y + 1))");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    CHK(settle(h));
-    if (h->kd_size <= 0) return fail("pfslam_search_wide: no map loaded");
-    if (h->nb > PF_SUM_TILE) return fail("pfslam_search_wide: n_beams > 4096 not supported");
-    if (h->cfg.map_res_x != h->cfg.map_res_y) return fail("pfslam_search_wide: map_res_x != map_res_y not supported");
-    SearchParams p;
-    p.res = h->cfg.map_res_x;
-    p.u = (p.res * p.res) * 0.0625f;
-    const float qf = rintf(pf::fdiv(opts->max_dist * opts->max_dist, p.u));
-    if (!(qf >= 1.0f && qf <= 65535.0f)) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "pfslam_search_wide: max_dist %g gives qcap %g in units of res^2 / 16; it must be 1 .. 65535", (double)opts->max_dist, (double)qf);
-        return fail(msg);
-    }
-    if (na * h->nb > PF_SEARCH_MAX_ENDS) return fail("pfslam_search_wide: more than 2^24 end points ((2 half_theta + 1) * n_beams)");
-    float c3[4] = {0, 0, 0, 0};
-    if (centre) {
-        memcpy(c3, centre, 12);
-    } else { // the handle's pose, as pfslam_get_pose reads it
-        HIPCHK(hipMemcpyAsync(c3, h->pose, 16, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (!(std::isfinite(c3[0]) && std::isfinite(c3[1]) && std::isfinite(c3[2]))) return fail("pfslam_search_wide: the centre (the handle's pose) must be finite");
-    }
-    p.cx = c3[0]; p.cy = c3[1]; p.ct = c3[2];
-    p.step_theta = opts->step_theta;
-    p.hx = opts->half_x; p.hy = opts->half_y; p.ht = opts->half_theta;
-    p.stride = opts->stride;
-    p.qcap = (int)qf;
-    p.nb = h->nb;
-    auto cell_bound = [&](float c, float d) { // rint((c + d) / res) as k_search_ends computes it, inside +-2^20
-        const float f = rintf(pf::fdiv(c + d, p.res));
-        return (int)std::min(std::max(f, -(float)PF_SEARCH_CELL_MAX), (float)PF_SEARCH_CELL_MAX);
-    };
-    p.lox = cell_bound(p.cx, -PF_LIDAR_RANGE); p.hix = cell_bound(p.cx, PF_LIDAR_RANGE);
-    p.loy = cell_bound(p.cy, -PF_LIDAR_RANGE); p.hiy = cell_bound(p.cy, PF_LIDAR_RANGE);
-    const long long W = (long long)p.hix - p.lox + 1 + 2LL * p.hx * p.stride, H = (long long)p.hiy - p.loy + 1 + 2LL * p.hy * p.stride;
-    if (W > PF_SEARCH_MAX_FIELD || H > PF_SEARCH_MAX_FIELD || W * H > PF_SEARCH_MAX_FIELD) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "pfslam_search_wide: the field would have %lld x %lld cells (40 m / res + 1 + 2 half stride a side); at most 2^26 cells", W, H);
-        return fail(msg);
-    }
-    p.cap = (int)(W * H);
-    // the top level: the smallest whose one block covers a heading's window, at most PF_WIDE_MAX_LEVEL
+    return bw[0] < 0 ? 0 : ((long long)bw[1] + bw[0] - 2LL * PF_SEARCH_BIAS + 1 + 2LL * p.hx * p.stride) *
+                               ((long long)bw[3] + bw[2] - 2LL * PF_SEARCH_BIAS + 1 + 2LL * p.hy * p.stride);
+}
+
+// The branch and bound of pfslam_search_wide and pfslam_search_best: end points, the field and its pyramid into the wide_* buffers, then
+// the descent.  `box` and `count` are words of the caller's state row, which it has memset; the caller brings its launches (checked here):
+//   score(leaf, n, nodes, fL) scores the batch's n nodes (fL: their level of the pyramid; leaf: std::true_type at level 0, the scoring
+//                             kernels' template argument) into wide_lb and into its own keys;
+//   expand(L, n, nodes, next) books the survivors' children in `next`, the buffer of level L - 1, and their number in *count.
+struct WideDescent { int top; long long bounded, scored, batches; }; // the top level; nodes scored above and at level 0; launches of `score`
+
+// stats[1 .. 6] of either entry point; stats[6]: the cells of the box as search_box computes it, none when no beam of any heading has a cell
+static void wide_stats(const SearchPlan &s, const WideDescent &d, const int bw[4], int64_t stats[8])
+{
+    stats[1] = (int64_t)s.cand;
+    stats[2] = d.bounded;
+    stats[3] = d.scored;
+    stats[4] = d.top;
+    stats[5] = d.batches;
+    stats[6] = search_box_cells(bw, s.p);
+}
+template <typename Score, typename Expand>
+static int wide_descend(pfslam_handle *h, const char *fn, const SearchPlan &s, int *box, int *count, Score score, Expand expand, WideDescent *d)
+{
+    const SearchParams &p = s.p;
     int top = 0;
-    while (top < PF_WIDE_MAX_LEVEL && (1LL << top) < std::max(nx, ny)) top++;
-    const long long n_top = na * (((nx - 1) >> top) + 1) * (((ny - 1) >> top) + 1);
+    while (top < PF_WIDE_MAX_LEVEL && (1LL << top) < std::max(s.nx, s.ny)) top++;
+    const long long n_top = s.na * (((s.nx - 1) >> top) + 1) * (((s.ny - 1) >> top) + 1);
     const int room = h->wide_frontier ? h->wide_frontier : PF_WIDE_FRONTIER; // nodes of one frontier buffer
     const size_t level = (size_t)p.cap + 2;                                  // cells of one level (+ the two spare cells of k_search_field)
-    // the feature's own device buffers; they grow when a call needs more
+    // scratch that either caller rewrites from the start of every call; it grows when a call needs more
     CHK(search_grow(&h->wide_field, &h->wide_field_cap, level * (size_t)(top + 1)));
-    CHK(search_grow(&h->wide_ends, &h->wide_ends_cap, (size_t)na * h->nb));
-    CHK(search_grow(&h->wide_nin, &h->wide_nin_cap, (size_t)na));
+    CHK(search_grow(&h->wide_ends, &h->wide_ends_cap, (size_t)s.na * h->nb));
+    CHK(search_grow(&h->wide_nin, &h->wide_nin_cap, (size_t)s.na));
     CHK(search_grow(&h->wide_nodes, &h->wide_nodes_cap, (size_t)room * (size_t)(top + 1)));
     CHK(search_grow(&h->wide_lb, &h->wide_lb_cap, (size_t)room));
-    if (!h->wide_state) CHK(dalloc(&h->wide_state, (size_t)4 + PF_SEARCH_OUT / 2)); // key, the four box words, the child count, the result row
-    unsigned long long *key = h->wide_state;
-    int *box = (int *)(h->wide_state + 1);
-    int *count = (int *)(h->wide_state + 3);
-    float *out = (float *)(h->wide_state + 4);
-    HIPCHK(hipMemsetAsync(h->wide_state, 0xff, 24, h->stream));
-    hipLaunchKernelGGL(k_search_ends, dim3((unsigned)na), dim3(256), 0, h->stream, (const float *)h->scan, p, h->trig, h->wide_ends, h->wide_nin, box);
+    hipLaunchKernelGGL(k_search_ends, dim3((unsigned)s.na), dim3(256), 0, h->stream, (const float *)h->scan, p, h->trig, h->wide_ends, h->wide_nin, box);
     HIPCHK(hipGetLastError());
     const unsigned cell_blocks = (unsigned)((p.cap + 255) / 256);
     hipLaunchKernelGGL(k_search_field, dim3(cell_blocks), dim3(256), 0, h->stream, kd_view(h), p, (const int *)box, h->wide_field);
@@ -232,7 +196,7 @@ extern "C" int pfslam_search_wide(pfslam_handle *h, const float centre[3], const
     // the next level's buffer whatever the pruning does.  With room to spare a level is one batch and the descent is level by level.
     // One wait per batch above level 0: the host reads how many children it left.
     long long have[PF_WIDE_MAX_LEVEL + 1] = {0}, done[PF_WIDE_MAX_LEVEL + 1] = {0};
-    long long bounded = 0, scored = 0, batches = 0;
+    *d = WideDescent{top, 0, 0, 0};
     have[top] = n_top;
     for (int L = top;;) {
         if (done[L] >= have[L]) {
@@ -249,31 +213,53 @@ extern "C" int pfslam_search_wide(pfslam_handle *h, const float centre[3], const
             nodes += done[L];
         }
         done[L] += n;
-        batches++;
-        (L ? bounded : scored) += n;
+        d->batches++;
+        (L ? d->bounded : d->scored) += n;
         const uint16_t *fL = h->wide_field + level * (size_t)L;
-        if (L)
-            hipLaunchKernelGGL(k_wide_score<false>, dim3((unsigned)n), dim3(64), 0, h->stream, (const int *)nodes, (const int2 *)h->wide_ends,
-                               (const int *)h->wide_nin, (const int *)box, (const uint16_t *)h->wide_field, fL, p, h->wide_lb, key);
-        else
-            hipLaunchKernelGGL(k_wide_score<true>, dim3((unsigned)n), dim3(64), 0, h->stream, (const int *)nodes, (const int2 *)h->wide_ends,
-                               (const int *)h->wide_nin, (const int *)box, (const uint16_t *)h->wide_field, fL, p, h->wide_lb, key);
+        L ? score(std::false_type{}, n, (const int *)nodes, fL) : score(std::true_type{}, n, (const int *)nodes, fL);
         HIPCHK(hipGetLastError());
         if (L == 0) continue;
         HIPCHK(hipMemsetAsync(count, 0, 4, h->stream));
-        hipLaunchKernelGGL(k_wide_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const int *)nodes, (const int *)h->wide_lb, n, L, p,
-                           (const unsigned long long *)key, h->wide_nodes + (size_t)room * (size_t)(L - 1), count);
+        expand(L, n, (const int *)nodes, h->wide_nodes + (size_t)room * (size_t)(L - 1));
         HIPCHK(hipGetLastError());
         int kids = 0;
         HIPCHK(hipMemcpyAsync(&kids, count, 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (kids < 0 || kids > 4 * n) return fail("pfslam_search_wide: internal: a batch left more children than four a node");
+        if (kids < 0 || kids > 4 * n) return fail(std::string(fn) + ": internal: a batch left more children than four a node");
         if (kids) {
             L--;
             have[L] = kids;
             done[L] = 0;
         }
     }
+    return 0;
+}
+
+extern "C" int pfslam_search_wide(pfslam_handle *h, const float centre[3], const pfslam_search_opts *opts, float pose_out[3], float info[8],
+                                  int64_t stats[8])
+{
+    if (!h || !opts || !pose_out || !info) return fail("pfslam_search_wide: bad argument");
+    SearchPlan s;
+    CHK(search_plan(h, "pfslam_search_wide", PF_FORM_WIDE, nullptr, centre, opts, &s));
+    const SearchParams &p = s.p;
+    if (!h->wide_state) CHK(dalloc(&h->wide_state, (size_t)4 + PF_SEARCH_OUT / 2)); // key, the four box words, the child count, the result row
+    unsigned long long *key = h->wide_state;
+    int *box = (int *)(h->wide_state + 1);
+    int *count = (int *)(h->wide_state + 3);
+    float *out = (float *)(h->wide_state + 4);
+    HIPCHK(hipMemsetAsync(h->wide_state, 0xff, 24, h->stream));
+    WideDescent d;
+    CHK(wide_descend(
+        h, "pfslam_search_wide", s, box, count,
+        [&](auto leaf, int n, const int *nodes, const uint16_t *fL) {
+            hipLaunchKernelGGL(k_wide_score<decltype(leaf)::value>, dim3((unsigned)n), dim3(64), 0, h->stream, nodes, (const int2 *)h->wide_ends,
+                               (const int *)h->wide_nin, (const int *)box, (const uint16_t *)h->wide_field, fL, p, h->wide_lb, key);
+        },
+        [&](int L, int n, const int *nodes, int *next) {
+            hipLaunchKernelGGL(k_wide_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nodes, (const int *)h->wide_lb, n, L, p,
+                               (const unsigned long long *)key, next, count);
+        },
+        &d));
     hipLaunchKernelGGL(k_search_result, dim3(1), dim3(1), 0, h->stream, (const unsigned long long *)key, (const int *)h->wide_nin, p, out);
     HIPCHK(hipGetLastError());
     unsigned long long st[4 + PF_SEARCH_OUT / 2];
@@ -284,16 +270,8 @@ extern "C" int pfslam_search_wide(pfslam_handle *h, const float centre[3], const
     if (stats) {
         int bw[4];
         memcpy(bw, st + 1, 16);
-        // the box as search_box computes it: empty when no beam of any heading has a cell
-        const long long cells = bw[0] < 0 ? 0 : ((long long)bw[1] + bw[0] - 2LL * PF_SEARCH_BIAS + 1 + 2LL * p.hx * p.stride) *
-                                                    ((long long)bw[3] + bw[2] - 2LL * PF_SEARCH_BIAS + 1 + 2LL * p.hy * p.stride);
         stats[0] = st[0] == ~0ull ? -1 : (int64_t)(st[0] & 0xffffffffull);
-        stats[1] = nx * ny * na;
-        stats[2] = bounded;
-        stats[3] = scored;
-        stats[4] = top;
-        stats[5] = batches;
-        stats[6] = cells;
+        wide_stats(s, d, bw, stats);
         stats[7] = 0;
     }
     return 0;

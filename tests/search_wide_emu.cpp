@@ -108,23 +108,11 @@ int main(int argc, char **argv) {
     fclose(f);
     if (room < 4) return 7;
     const pf::KdView tree{hot.data(), z.data(), parent.data(), w.data(), planar};
-    // what pfslam_search_wide derives from its arguments (csrc/pfslam_search_wide.hip.inc)
+    // what every entry point derives from its arguments: the library's own search_derive (csrc/pfslam_search.hip.inc), cut out with the kernels
     SearchParams p;
-    p.cx = fl[0]; p.cy = fl[1]; p.ct = fl[2]; p.step_theta = fl[3]; p.res = fl[5];
-    p.hx = hd[4]; p.hy = hd[5]; p.ht = hd[6]; p.stride = hd[7]; p.nb = nb;
-    p.u = (p.res * p.res) * 0.0625f;
-    const float qf = rintf(pf::fdiv(fl[4] * fl[4], p.u));
-    if (!(qf >= 1.0f && qf <= 65535.0f)) return 5;
-    p.qcap = (int)qf;
-    auto cell_bound = [&](float c, float d) {
-        const float g = rintf(pf::fdiv(c + d, p.res));
-        return (int)std::min(std::max(g, -(float)PF_SEARCH_CELL_MAX), (float)PF_SEARCH_CELL_MAX);
-    };
-    p.lox = cell_bound(p.cx, -PF_LIDAR_RANGE); p.hix = cell_bound(p.cx, PF_LIDAR_RANGE);
-    p.loy = cell_bound(p.cy, -PF_LIDAR_RANGE); p.hiy = cell_bound(p.cy, PF_LIDAR_RANGE);
-    const long long W = (long long)p.hix - p.lox + 1 + 2LL * p.hx * p.stride, H = (long long)p.hiy - p.loy + 1 + 2LL * p.hy * p.stride;
-    if (W * H > (1 << 26)) return 6;
-    p.cap = (int)(W * H);
+    SearchWhy why;
+    const SearchRefusal no = search_derive(fl[5], nb, &fl[0], hd[4], hd[5], hd[6], hd[7], fl[3], fl[4], &p, &why);
+    if (no != SEARCH_FITS) return no == SEARCH_QCAP ? 5 : 6;
     const long long nx = 2LL * p.hx + 1, ny = 2LL * p.hy + 1, na = 2LL * p.ht + 1;
     int top = 0;
     while (top < PF_WIDE_MAX_LEVEL && (1LL << top) < std::max(nx, ny)) top++;

@@ -167,6 +167,42 @@ def test_pfslam_search_before_and_after_returns_identical_bits(pkg, world):
     h.close()
 
 
+def test_one_state_row_serves_every_entry_point_in_any_order(pkg, world):
+    """pfslam_search, pfslam_search_scan and the two cov forms share one volume runner and one device state row (key, box words, result row,
+    point count, cov_out).  One handle runs the six entry points of the family in order, then in reverse, a refused call of a plain or a
+    cov form behind each: every result is, bit for bit, that of the same call on a fresh handle -- no call reads what another left."""
+    nb = 65
+    ref, scan = world["ref"][:nb].copy(), world["scan"][:nb].copy()
+    calls = [("search", lambda h: h.search(CENTRE, scores=True, **SMALL)),
+             ("search_scan", lambda h: h.search_scan(ref, REF_POSE, scan, CENTRE, scores=True, **SMALL)),
+             ("search_cov", lambda h: h.search_cov(CENTRE, scores=True, **SMALL)),
+             ("search_scan_cov", lambda h: h.search_scan_cov(ref, REF_POSE, None, CENTRE, scores=True, **SMALL)),    # (the handle's scan)
+             ("search_wide", lambda h: h.search_wide(CENTRE, **SMALL)),
+             ("search_best", lambda h: h.search_best(CENTRE, **SMALL))]
+    refused = [("pfslam_search", lambda h: h.search(CENTRE, stride=0)),
+               ("pfslam_search_scan", lambda h: h.search_scan(ref, REF_POSE, scan, CENTRE, stride=0)),
+               ("pfslam_search_cov", lambda h: h.search_cov(CENTRE, stride=0)),
+               ("pfslam_search_scan_cov", lambda h: h.search_scan_cov(ref, REF_POSE, scan, CENTRE, stride=0))]
+
+    def frozen(out):
+        return {k: (np.asarray(v).dtype.str, np.asarray(v).shape, np.asarray(v).tobytes()) for k, v in out.items()}
+
+    want = {}
+    for name, call in calls:
+        fresh = mapped(pkg, world, nb)
+        want[name] = frozen(call(fresh))
+        fresh.close()
+    h = mapped(pkg, world, nb)
+    for n, (name, call) in enumerate(calls + calls[::-1]):
+        got = call(h)
+        assert frozen(got) == want[name], "call %d, %s: %r" % (n, name, sorted(k for k, v in frozen(got).items() if v != want[name][k]))
+        who, refuse = refused[n % 4]
+        with pytest.raises(pkg.PfSlamError, match=who + ": stride must be 1 .. 64"):
+            refuse(h)
+    assert h.search(CENTRE, **SMALL)["status"] == 0 and h.search_best(CENTRE, **SMALL)["found"] >= 1
+    h.close()
+
+
 # ---- 4. read-only ------------------------------------------------------------------------------------------------------------------------------------
 def test_behind_frames_in_flight_the_calls_read_and_change_nothing(pkg):
     torch = pytest.importorskip("torch")

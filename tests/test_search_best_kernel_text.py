@@ -58,7 +58,7 @@ def emu(tmp_path_factory):
     for src, first, last in cuts:
         assert src.count(first) == 1 and src.count(last) == 1, "the kernel text has moved: %r" % first
         text += src[src.index(first):src.index(last, src.index(first))]
-    for name in ("k_search_ends", "k_search_field", "k_wide_pyramid", "k_wide_top", "k_best_score", "k_best_thr", "k_best_expand", "k_best_compact",
+    for name in ("search_derive", "k_search_ends", "k_search_field", "k_wide_pyramid", "k_wide_top", "k_best_score", "k_best_thr", "k_best_expand", "k_best_compact",
                  "k_best_rows", "kd_nearest_exact"):
         assert name in text
     (d / "search_best_kernel_text.inc").write_text(text)

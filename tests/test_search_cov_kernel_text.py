@@ -83,7 +83,7 @@ def emu(tmp_path_factory):
     for src, first, last in cuts:
         assert src.count(first) == 1 and src.count(last) == 1, "the kernel text has moved: %r" % first
         text += src[src.index(first):src.index(last, src.index(first))]
-    for name in ("k_search_ends", "k_search_score", "k_search_result", "k_scan_points", "k_scan_fill", "k_scan_splat", "est_moments", "est_centred",
+    for name in ("search_derive", "k_search_ends", "k_search_score", "k_search_result", "k_scan_points", "k_scan_fill", "k_scan_splat", "est_moments", "est_centred",
                  "est_finish", "k_cov_moments", "k_cov_centred", "k_cov_final", "k_cov_small"):
         assert name in text
     (d / "search_cov_kernel_text.inc").write_text(text)

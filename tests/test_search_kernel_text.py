@@ -58,7 +58,7 @@ def emu(tmp_path_factory):
     for src, first, last in cuts:
         assert src.count(first) == 1 and src.count(last) == 1, "the kernel text has moved: %r" % first
         text += src[src.index(first):src.index(last, src.index(first))]
-    for name in ("k_search_ends", "k_search_field", "k_search_score", "k_search_result", "kd_nearest_exact"):
+    for name in ("search_derive", "k_search_ends", "k_search_field", "k_search_score", "k_search_result", "kd_nearest_exact"):
         assert name in text
     (d / "search_kernel_text.inc").write_text(text)
     defs = [re.search(r"^#define %s .*$" % name, main, re.M).group(0) for name in ("PF_LIDAR_RANGE", "PF_SVD_EPSILON")]
