@@ -247,6 +247,9 @@ __global__ __launch_bounds__(PF_MARK_THREADS) void k_cells_mark(const pf::KdGrou
             if (k < PF_MARK_CLAIMS) s_claim[k] = idx;
             else { // more new cells than the workgroup can hold: append one by one
                 const int pos = atomicAdd(&cs[PF_CS_COUNT], 1);
+                // (booked like the collected ones: which workgroup wins a cell is a race, so a count that left these out differed from run
+                // to run wherever a workgroup overflowed -- tests/test_gpu_observers.py compares it between runs)
+                atomicAdd(&cs[PF_CS_CUR_CLAIMED], 1);
                 if (pos < cs[PF_CS_LIST_CAP]) list[pos] = idx;
                 else { // list full: the cell gets no row until the next wipe
                     atomicExch(&tab[idx], PF_CELL_FALLBACK);

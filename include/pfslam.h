@@ -288,8 +288,10 @@ int pfslam_device_ptr(pfslam_handle *h, int which, void **ptr, size_t *bytes);
  * pfslam_time_score_kd: `iters` back-to-back scoring passes (lane order + scan-match kernel + partial-sum reduce, i.e. all of
  *   pfslam_score_kd's device work) between two HIP events on the handle's stream; average milliseconds per pass.
  * pfslam_set_timing: 0 = off; 1 = HIP events on the handle's stream bracket every launch of the scan-match kernel (only that
- *   kernel) inside pfslam_step / pfslam_shard_begin; 2 = additionally the four phases the reference times per frame
+ *   kernel) inside pfslam_step / pfslam_shard_score; 2 = additionally the four phases the reference times per frame
  *   (kernel.cu:1727-1760: motion, measurement incl. ICP, map update incl. its host part, resample).  Resets the accumulators.
+ *   Mode 2 is for pfslam_step only -- its frames leave the round-5 frame for the staged chain, with the same results -- and
+ *   pfslam_shard_disperse refuses a handle in that mode.
  * pfslam_get_timers -> out[2k] = total ms, out[2k+1] = count, k = 0 scan-match kernel, 1 motion, 2 measurement, 3 map,
  *   4 resample, 5 the planning launches that precede the scan-match kernel (pose boxes + shared-prefix plan).
  * pfslam_score_census: what one scoring launch on the handle's CURRENT particles, scan and map issues, counted by a counting
@@ -334,7 +336,8 @@ int pfslam_plan_stats(pfslam_handle *h, double out[10]);
  * [0 .. 13] are zero when the last scoring pass did not use cell rows. */
 int pfslam_cell_stats(pfslam_handle *h, double out[16]);
 /* mean duration (ms) of the 2-D scan-match kernel alone and of the whole 2-D scoring pass (kernel + partial sums + min / max / argmax +
- * weights) over `iters` launches each, HIP events on the handle's stream */
+ * weights) over `iters` launches each, HIP events on the handle's stream.  The weights (and their host mirror) are put back behind the
+ * last pass: like pfslam_time_score_kd the call leaves particles, pose and maps as it found them. */
 int pfslam_time_score_grid(pfslam_handle *h, int iters, float *ms_kernel, float *ms_pass);
 int pfslam_set_variant(pfslam_handle *h, int variant);
 /* Transcendentals.  0 (default) = the specification of csrc/pf_math.h: fixed sequences of IEEE double operations rounded once, which the
