@@ -28,7 +28,7 @@ SYMBOLS = [
     "pfslam_set_serial", "pfslam_set_trig", "pfslam_set_resampler", "pfslam_estimate", "pfslam_debug_check_cells", "pfslam_set_probe", "pfslam_get_probe", "pfslam_probe_name", "pfslam_frame_mode",
     "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch", "pfslam_search", "pfslam_search_default_opts", "pfslam_search_scan", "pfslam_search_wide",
     "pfslam_search_cov", "pfslam_search_scan_cov", "pfslam_search_cov_default_opts", "pfslam_search_best", "pfslam_search_best_default_opts",
-    "pfslam_cast", "pfslam_cast_default_opts", "pfslam_map_raster",
+    "pfslam_cast", "pfslam_cast_default_opts", "pfslam_map_raster", "pfslam_cast_score", "pfslam_cast_score_default_opts",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
 
@@ -71,6 +71,13 @@ class CastOpts(C.Structure):
                 ("reserved_", C.c_int32 * 3)]
 
 
+class CastScoreOpts(C.Structure):
+    """pfslam_cast_score_opts (include/pfslam.h)."""
+    _fields_ = [("tol", C.c_float), ("clip", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float), ("count_miss", C.c_int32), ("source", C.c_int32),
+                ("reserved_", C.c_int32 * 2)]
+
+
+CAST_SCORE_COLUMNS = ("valid", "agree", "through", "short", "miss", "q1", "q2", "cost")
 REGISTER_STATUS = {0: "max_iters", 1: "converged", 2: "too_few_pairs", 3: "not_finite"}
 
 
@@ -196,6 +203,9 @@ def load():
     L.pfslam_cast_default_opts.argtypes = [vp]
     L.pfslam_cast.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.pfslam_map_raster.argtypes = [vp, vp, vp, vp, C.c_size_t]
+    L.pfslam_cast_score_default_opts.restype = None
+    L.pfslam_cast_score_default_opts.argtypes = [vp]
+    L.pfslam_cast_score.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.pfslam_debug_check_cells.argtypes = [vp, vp]
     L.pfslam_set_probe.argtypes = [vp, i32]
     L.pfslam_get_probe.argtypes = [vp, vp, i32, vp, vp]
@@ -746,6 +756,50 @@ class PfSlam:
         if W * H:
             _chk(self.L.pfslam_map_raster(self._h, C.byref(o), _p(stats), _p(occ), W * H), "pfslam_map_raster")
         return tuple(int(v) for v in stats[4:8]), occ
+
+    def cast_score(self, poses=None, scan=None, particles=False, classes=False, **opts):
+        """The beam-model score of each of the m x 3 `poses` (None: the handle's pose; particles=True: the handle's own particles, read on
+        the device): the measured `scan` (None: the handle's scan) against the scan the map predicts from the pose, reduced to eight
+        integers per pose on the device (include/pfslam.h, pfslam_cast_score).  Options by name over the defaults of both structures:
+        the cast's (max_range, w_min, inflate, skip_cells; no_hit is not read) and tol, clip, z_min, z_max, count_miss.  Returns rows (m x 8 int32), its
+        columns by name (valid, agree, through, short, miss, q1, q2, cost), rms (float64: sqrt(q2 / agree) in metres over the agreeing
+        beams, nan where none agrees), classes (m x n_beams uint8 with classes=True, else None), best (the row picked, -1 for none) and
+        stats (int64[8], as cast()'s).  Reads the handle's map, scan and particles, writes none of its state."""
+        ours = ("tol", "clip", "z_min", "z_max", "count_miss")
+        co = self._cast_opts("cast_score", {k: v for k, v in opts.items() if k not in ours})
+        so = CastScoreOpts()
+        self.L.pfslam_cast_score_default_opts(C.byref(so))
+        for k in ours:
+            if k in opts:
+                setattr(so, k, opts[k])
+        so.source = 1 if particles else 0
+        ps = None
+        m = self.n if particles else 1
+        if poses is not None:
+            ps = np.ascontiguousarray(poses, dtype=np.float32)
+            if ps.ndim == 1 and ps.size == 3:
+                ps = ps.reshape(1, 3)
+            if ps.ndim != 2 or ps.shape[1] != 3:
+                raise ValueError("cast_score(): poses must be m x (x, y, theta), got shape %r" % (ps.shape,))
+            m = len(ps)
+        sc = None
+        if scan is not None:
+            sc = np.ascontiguousarray(scan, dtype=np.float32).ravel()
+            if sc.size != self.nb:
+                raise ValueError("cast_score(): scan must have n_beams = %d ranges, got %d" % (self.nb, sc.size))
+        held = m if 1 <= m <= 65536 else 0                 # (a call outside the caps is the library's to refuse)
+        rows = np.zeros((held, 8), np.int32)
+        cl = np.zeros((held if m * self.nb <= 1 << 24 else 0, self.nb), np.uint8) if classes else None
+        best = C.c_int(-1)
+        stats = np.zeros(8, np.int64)
+        _chk(self.L.pfslam_cast_score(self._h, None if ps is None else _p(ps), m, None if sc is None else _p(sc), C.byref(co), C.byref(so), _p(rows),
+                                      None if cl is None else _p(cl), C.byref(best), _p(stats)), "pfslam_cast_score")
+        out = {"rows": rows, "classes": cl, "best": int(best.value), "stats": stats}
+        for k, name in enumerate(CAST_SCORE_COLUMNS):
+            out[name] = rows[:, k]
+        with np.errstate(all="ignore"):
+            out["rms"] = np.sqrt(rows[:, 6].astype(np.float64) / rows[:, 1]) * float(np.float32(so.tol) * np.float32(0.0625))
+        return out
 
     def _cov_opts(self, sigma):
         q = CovOpts()

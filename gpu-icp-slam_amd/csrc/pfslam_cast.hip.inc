@@ -101,8 +101,9 @@ __device__ __forceinline__ int cast_reach(int q, int adm, int n)
     return ((2 * q - 1) * n + 2 * adm - 1) / (2 * adm);
 }
 
-// The cast.  One lane per ray, adjacent lanes the adjacent beams of one pose: their walks start in the same cell and fan out, so a wave's
-// loads fall into few tiles.  The walk's cell is a closed form of its index t (the specification), which lets a ray jump:
+// The walk of one ray, for k_cast_rays and for k_cast_score (pfslam_cast_score.hip.inc): from the pose (x, y) towards (x + wx, y + wy); 1
+// and the hit's cell and range, or 0 and the three left as they were.  The walk's cell is a closed form of its index t (the
+// specification), which lets a ray jump:
 //   * the t for which the ray is inside the box form one interval, found up front -- a ray that starts outside enters by it;
 //   * an empty tile is left at once, for the first t that leaves it along either axis (SKIP).
 // Inside a tile that holds something the walk steps cell by cell; between two jumps the minor offset is carried with its remainder
@@ -110,23 +111,14 @@ __device__ __forceinline__ int cast_reach(int q, int adm, int n)
 // t = skip .. n is tested against the box and the raster.  The test against the box stays in both forms: it keeps the loads inside the
 // buffer whatever the arithmetic does.
 template <bool SKIP>
-__global__ __launch_bounds__(256) void k_cast_rays(const float *__restrict__ poses, int rays, CastParams p, CastBox B,
-                                                   const unsigned long long *__restrict__ tiles, float *__restrict__ ranges,
-                                                   int *__restrict__ cells, int *st)
+__device__ __forceinline__ int cast_walk(float x, float y, float wx, float wy, const CastParams &p, const CastBox &B,
+                                         const unsigned long long *__restrict__ tiles, int &hx, int &hy, float &range)
 {
-    const int id = blockIdx.x * 256 + threadIdx.x;
-    const bool live = id < rays; // (a lane behind the last ray stays for the wave's count of the hits; it casts nothing)
-    const int r = live ? id / p.nb : 0, b = live ? id - r * p.nb : 0;
-    const float x = poses[3 * r], y = poses[3 * r + 1], theta = poses[3 * r + 2];
-    float wx, wy;
-    pf::clean_lidar_scan(b, p.max_range, theta, wx, wy, p.trig);
     const float fsx = rintf(pf::fdiv(x, p.res_x)), fex = rintf(pf::fdiv(x + wx, p.res_x));
     const float fsy = rintf(pf::fdiv(y, p.res_y)), fey = rintf(pf::fdiv(y + wy, p.res_y));
     const float lim = (float)PF_CAST_CELL_MAX;
-    int hx = PF_CAST_MISS, hy = PF_CAST_MISS;
-    float range = p.no_hit;
     int hit = 0;
-    if (live && fabsf(fsx) <= lim && fabsf(fex) <= lim && fabsf(fsy) <= lim && fabsf(fey) <= lim) { // (false for a NaN and for an infinity)
+    if (fabsf(fsx) <= lim && fabsf(fex) <= lim && fabsf(fsy) <= lim && fabsf(fey) <= lim) { // (false for a NaN and for an infinity)
         const int sx = (int)fsx, sy = (int)fsy, dx = (int)fex - sx, dy = (int)fey - sy;
         const int adx = abs(dx), ady = abs(dy), n = max(adx, ady);
         const bool xmajor = adx >= ady;
@@ -192,6 +184,25 @@ __global__ __launch_bounds__(256) void k_cast_rays(const float *__restrict__ pos
             }
         }
     }
+    return hit;
+}
+
+// The cast.  One lane per ray, adjacent lanes the adjacent beams of one pose: their walks start in the same cell and fan out, so a wave's
+// loads fall into few tiles.
+template <bool SKIP>
+__global__ __launch_bounds__(256) void k_cast_rays(const float *__restrict__ poses, int rays, CastParams p, CastBox B,
+                                                   const unsigned long long *__restrict__ tiles, float *__restrict__ ranges,
+                                                   int *__restrict__ cells, int *st)
+{
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    const bool live = id < rays; // (a lane behind the last ray stays for the wave's count of the hits; it casts nothing)
+    const int r = live ? id / p.nb : 0, b = live ? id - r * p.nb : 0;
+    const float x = poses[3 * r], y = poses[3 * r + 1], theta = poses[3 * r + 2];
+    float wx, wy;
+    pf::clean_lidar_scan(b, p.max_range, theta, wx, wy, p.trig);
+    int hx = PF_CAST_MISS, hy = PF_CAST_MISS;
+    float range = p.no_hit;
+    int hit = live ? cast_walk<SKIP>(x, y, wx, wy, p, B, tiles, hx, hy, range) : 0;
     for (int off = 32; off >= 1; off >>= 1) hit += __shfl_xor(hit, off, 64);
     if ((threadIdx.x & 63) == 0 && hit > 0) atomicAdd(&st[6], hit); // one add per wave
     if (!live) return;

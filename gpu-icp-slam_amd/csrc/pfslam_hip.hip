@@ -191,6 +191,12 @@ struct pfslam_handle {
     int *cast_cells = nullptr, *cast_state = nullptr;
     uint8_t *cast_occ = nullptr;
     size_t cast_tiles_cap = 0, cast_poses_cap = 0, cast_ranges_cap = 0, cast_cells_cap = 0, cast_occ_cap = 0;
+    // pfslam_cast_score's own buffers (the raster, the state words and the uploaded poses are pfslam_cast's above), grown the same way: an
+    // uploaded scan (n_beams), the rows (m x 8) and the class bytes (m x n_beams, only for a call that asks for them)
+    float *cscore_scan = nullptr;
+    int *cscore_rows = nullptr;
+    uint8_t *cscore_classes = nullptr;
+    size_t cscore_scan_cap = 0, cscore_rows_cap = 0, cscore_classes_cap = 0;
     float *est_part = nullptr; // pfslam_estimate: 11 tile sums per 4096-particle tile of the GLOBAL cloud, then the 16 output floats
     // grid path
     int8_t *grid = nullptr;
@@ -1092,7 +1098,7 @@ extern "C" int pfslam_destroy(pfslam_handle *h)
                     h->fit, h->fit_i, h->partial, h->mkey, h->order2, h->cells, h->stats, h->pose, h->start, h->icp_tar, h->icp_cor, h->icp_dbg,
                     h->free_mask, h->blk_cnt, h->wall_cell, h->free_cell, h->wall_pts, h->free_pts,
                     h->wall_c, h->free_c, h->counts, h->tile_r, h->tile_r2, h->sums, h->cdf,
-                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->srch_field, h->srch_ends, h->srch_nin, h->srch_scores, h->srch_state, h->wide_field, h->wide_ends, h->wide_nin, h->wide_nodes, h->wide_lb, h->wide_state, h->best_tab, h->best_list, h->best_state, h->scan_in, h->scan_pts, h->cov_part, h->cast_tiles, h->cast_poses, h->cast_ranges, h->cast_cells, h->cast_state, h->cast_occ, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
+                    h->chunk_max, h->tile_tot, h->tile_off, h->tile_pmax, h->src, h->est_part, h->reg_tar, h->reg_cor, h->reg_out, h->regb_in, h->regb_out, h->srch_field, h->srch_ends, h->srch_nin, h->srch_scores, h->srch_state, h->wide_field, h->wide_ends, h->wide_nin, h->wide_nodes, h->wide_lb, h->wide_state, h->best_tab, h->best_list, h->best_state, h->scan_in, h->scan_pts, h->cov_part, h->cast_tiles, h->cast_poses, h->cast_ranges, h->cast_cells, h->cast_state, h->cast_occ, h->cscore_scan, h->cscore_rows, h->cscore_classes, h->grid, h->d_count, h->wall_leaf, h->kd_state, h->d_sigma};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (h->own_global) {
@@ -2504,3 +2510,4 @@ static int frame_v2_finish(pfslam_handle *h);
 #include "pfslam_search_wide.hip.inc"
 #include "pfslam_search_best.hip.inc"
 #include "pfslam_cast.hip.inc"
+#include "pfslam_cast_score.hip.inc"

@@ -331,6 +331,24 @@ bool pfslamCastScan(glm::vec3 pose, float *ranges, int *hits)
     if (hits) *hits = (int)stats[1];
     return true;
 }
+bool pfslamCastScore(const glm::vec3 *poses, int m, int *rows, int *best)
+{
+    if (!g_handle || !poses || !rows) return false;
+    pfslam_cast_opts c;
+    pfslam_cast_default_opts(&c);
+    pfslam_cast_score_opts o;
+    pfslam_cast_score_default_opts(&o);
+    std::vector<float> p((size_t)(m > 0 ? m : 0) * 3);
+    for (int r = 0; r < m; r++) {
+        p[3 * (size_t)r] = poses[r].x; p[3 * (size_t)r + 1] = poses[r].y; p[3 * (size_t)r + 2] = poses[r].z;
+    }
+    static_assert(sizeof(int) == sizeof(int32_t), "rows are int32");
+    if (pfslam_cast_score(g_handle, p.data(), m, nullptr, &c, &o, rows, nullptr, best, nullptr)) { // (an empty map is a state of the filter, not a failure of the program)
+        fprintf(stderr, "pfslamCastScore: %s\n", pfslam_last_error());
+        return false;
+    }
+    return true;
+}
 bool pfslamSearchScan(const float *ref_scan, glm::vec3 ref_pose, glm::vec3 &pose, int *index, const float *scan)
 {
     if (!g_handle) return false;

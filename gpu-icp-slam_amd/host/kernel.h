@@ -111,6 +111,13 @@ int pfslamSearchBest(glm::vec3 centre, float half_metres, float half_radians, in
 // hit.  Reads the filter, changes nothing in it; like getPCData it first waits for the frames in flight.  hits may be null.  false (and a
 // line on stderr): no live filter or no map yet; the outputs are then untouched.
 bool pfslamCastScan(glm::vec3 pose, float *ranges, int *hits);
+// The beam-model score of `m` poses (no reference counterpart; include/pfslam.h, pfslam_cast_score, the default options of the cast and
+// of the score): the live filter's scan compared beam by beam with the scan its map predicts from each pose, reduced on the device.
+// rows[r * 8 + ..] = valid beams, agree (within 0.1 m), through (the measured beam ends behind a mapped wall), short, valid misses, Q1,
+// Q2, cost; *best the row with the smallest cost among those with an agreeing beam, -1 when there is none.  Reads the filter, changes
+// nothing in it; like getPCData it first waits for the frames in flight.  best may be null.  false (and a line on stderr): no live
+// filter, no map yet or m outside 1 .. 65536; the outputs are then untouched.
+bool pfslamCastScore(const glm::vec3 *poses, int m, int *rows /* m x 8 */, int *best);
 // Map export for an end-to-end comparison: the point-cloud map as the reference's viewer filters it
 // (nodes with w > -100, main.cpp:269-284) -> PREFIX.kd.bin (float x, y, z, w per point, in node order) + PREFIX.kd.csv, and
 // the 2-D occupancy grid -> PREFIX.grid.i8 (dim.x * dim.y signed bytes, cell (x, y) at x * dim.x + y) + PREFIX.grid.pgm

@@ -1,5 +1,5 @@
 // replay_main.cpp -- headless counterpart of the reference's main loop (main.cpp:47-96, 175-229):
-//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [cast=1] [export=PREFIX]
+//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [cast=1] [castscore=1] [export=PREFIX]
 //     grid           the 2-D occupancy-grid stages instead of the point-cloud ones
 //     loop           UpdateTopology + CheckLoopClosure at the end of every frame (kernel.cu:1750-1751, commented out in
 //                    the reference's shipped step); loop-closure proposals are printed per frame
@@ -24,6 +24,8 @@
 //     cast=1         a further line per frame: "cast <frame> hits <n> agree <k>": pfslamCastScan from the frame's pose through the frame's map,
 //                    the beams that hit, and the beams whose cast range is within 0.1 m of the scan's ("cast <frame> none" when the call fails or
 //                    the scan does not have the filter's 1081 beams)
+//     castscore=1    a further line per frame: "castscore <frame> valid <n> agree <a> through <t> short <s> miss <m> cost <c>": pfslamCastScore of
+//                    the frame's pose, the frame's scan against the frame's map ("castscore <frame> none" when the call fails)
 //     export=PREFIX  after the last frame: the map as the reference's viewer filters it (KD nodes with w > -100,
 //                    main.cpp:269-284) and the occupancy grid -> PREFIX.kd.bin / .kd.csv / .grid.i8 / .grid.pgm
 // iteration 0: Free + Init; then particleFilter(pbo=NULL, ++iteration, lidar) until the scans run out.
@@ -40,7 +42,7 @@
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [cast=1] [export=PREFIX]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [cast=1] [castscore=1] [export=PREFIX]\n", argv[0]);
         return 1;
     }
     Scene *scene = new Scene(argv[1]);
@@ -48,7 +50,7 @@ int main(int argc, char **argv)
     size_t last = lidar->scans.size() - 1;
     bool loop = false, estimate = false;
     int register_iters = 0, multistart_iters = 0, search = 0;
-    bool odometry = false, cast = false;
+    bool odometry = false, cast = false, castscore = false;
     std::string export_prefix;
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "grid") == 0) pfslamUseGridMap(true);
@@ -60,6 +62,7 @@ int main(int argc, char **argv)
         else if (strncmp(argv[i], "search=", 7) == 0) search = atoi(argv[i] + 7);
         else if (strncmp(argv[i], "odometry=", 9) == 0) odometry = atoi(argv[i] + 9) != 0;
         else if (strncmp(argv[i], "cast=", 5) == 0) cast = atoi(argv[i] + 5) != 0;
+        else if (strncmp(argv[i], "castscore=", 10) == 0) castscore = atoi(argv[i] + 10) != 0;
         else if (strncmp(argv[i], "export=", 7) == 0) export_prefix = argv[i] + 7;
         else if (atoi(argv[i]) > 0) last = std::min(last, (size_t)atoi(argv[i]));
     }
@@ -188,6 +191,13 @@ int main(int argc, char **argv)
             } else {
                 printf("cast %zu none\n", iteration);
             }
+        }
+        if (castscore) {
+            int row[8];
+            if (pfslamCastScore(&pos, 1, row, nullptr))
+                printf("castscore %zu valid %d agree %d through %d short %d miss %d cost %d\n", iteration, row[0], row[1], row[2], row[3], row[4], row[7]);
+            else
+                printf("castscore %zu none\n", iteration);
         }
     }
     printf("mean step+readback %.3f ms over %zu frames\n", iteration ? total_ms / iteration : 0.0, iteration);

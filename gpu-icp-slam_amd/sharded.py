@@ -206,6 +206,11 @@ class ShardedSlam:
         rank gets the unsharded bits with no collective."""
         return self.eng.cast(poses, cells, **opts)
 
+    def cast_score(self, poses=None, scan=None, particles=False, classes=False, **opts):
+        """The beam-model score of poses against the measured scan (pfslam_cast_score): passed through like cast.  With particles=True a
+        rank scores its own shard, read where it lives; nothing is gathered."""
+        return self.eng.cast_score(poses, scan, particles, classes, **opts)
+
     def map_raster(self, **opts):
         """The occupancy raster pfslam_cast walks through (pfslam_map_raster): passed through like cast."""
         return self.eng.map_raster(**opts)

@@ -35,6 +35,7 @@
  *   pfslam_search_wide                 no counterpart: the same winner over windows of up to 2^31 - 1 candidates, by branch and bound
  *   pfslam_search_best                 no counterpart: the best candidate of each of the N best cells of such a window, by the same descent
  *   pfslam_cast, pfslam_map_raster     no counterpart: the ranges the map predicts for a scan from any pose, by a walk through a raster of its nodes; that raster
+ *   pfslam_cast_score                  no counterpart: a measured scan compared beam by beam with those ranges, reduced on the device to eight integers per pose, and the pick
  *   pfslam_topology_update, find_walls,
  *   check_loop_closure, get_topology   UpdateTopology / FindWalls / CheckLoopClosure   kernel.cu:623-795
  *   pfslam_shard_disperse / score / weights / finish   particleFilter split where a multi-GPU caller places its three
@@ -839,6 +840,70 @@ int pfslam_cast(pfslam_handle *h, const float *poses /* m x 3; NULL = the handle
                 int32_t *cells_out /* NULL or m x n_beams x 2 */, int64_t stats[8] /* may be NULL */);
 int pfslam_map_raster(pfslam_handle *h, const pfslam_cast_opts *opts, int64_t stats[8],
                       uint8_t *occ /* NULL or W * H bytes */, size_t cap);
+/* pfslam_cast_score: the beam-model score of poses -- a measured scan compared beam by beam with the scan pfslam_cast expects from each
+ * pose, fused into the cast and reduced per pose on the device (no reference counterpart).  The rest of the pose family (pfslam_search*,
+ * pfslam_register*, the filter's own scan match) asks where a beam ENDS; a pose whose beams pass through mapped walls can score well on
+ * that question (the symmetric-room and corridor ambiguities pfslam_search_best lists).  This call separates them, and it is the last
+ * link of search_best -> register_batch -> pick.  The poses are a list, the handle's pose, or the handle's own particles, which are read
+ * where they live; what comes back is eight integers per pose, not m x n_beams ranges.
+ *   tol         m: |measured - expected| <= tol agrees; finite, >= 1e-4
+ *   clip        m: the residual saturates here; finite
+ *   z_min,z_max a measured range takes part iff z >= z_min && z <= z_max (false for a NaN); finite, z_min <= z_max
+ *   count_miss  0 / 1: a measured beam whose ray hits nothing costs qcap
+ *   source      0 = `poses` (NULL: the handle's pose, m == 1), 1 = the handle's own particles (poses NULL, m == n_particles)
+ *   reserved_   must be 0
+ * All arithmetic is float, one rounding per operation, in the order written, no contraction; fdiv is the correctly rounded division;
+ * integers are exact.
+ *   expected    the raster, the ray, the walk and the range are pfslam_cast's, word for word, for the same `cast` options: for pose r and
+ *               beam b, hit and e are exactly what pfslam_cast reports.  cast->no_hit is not read.  pfslam_set_trig is honoured.
+ *   unit        u = tol * 0.0625f; qcap = (int)rintf(fdiv(clip, u)), refused unless 16 <= qcap <= 32767.
+ *   measured    z = scan[b] (scan_host, or the handle's scan when that is NULL); valid = z >= z_min && z <= z_max.
+ *   residual    d = z - e, a = fabsf(d), fq = rintf(fdiv(a, u)), q = fq >= (float)qcap ? qcap : (int)fq (the compare comes before the
+ *               conversion: a huge a has a defined result).
+ *   class       of a beam, as written to classes_out[r * n_beams + b]: 0 not valid; 1 valid, the ray misses; 2 agree: valid, hit,
+ *               a <= tol; 3 through: valid, hit, d > tol (the measured beam ends behind a mapped wall); 4 short: every other valid hit.
+ *   row r       rows_out[r * 8 + ..]: [0] valid beams, [1] agree, [2] through, [3] short, [4] valid misses, [5] Q1 = sum of q over the
+ *               classes 2 .. 4, [6] Q2 = sum of q * q over class 2 (q <= 16 there, exactly), [7] cost = Q1 + (count_miss ? qcap * [4] : 0).
+ *               Everything is an integer below 2^31 (4096 x 32767): exact in any summation order, like the search family's scores.
+ *   *best       decided on the host from the rows alone: eligible rows have [1] > 0; among them the smallest cost wins, then the larger
+ *               [1], then the lowest row; -1 when no row is eligible.  [0] depends on the scan only, so costs compare across rows.
+ *   stats       pfslam_cast's eight specified values; [1] counts every ray that hits, whether its beam is valid or not.
+ *   source 1    row r is the local particle r of the handle, read on the device from the pose block (pfslam_device_ptr buffer 16,
+ *               [x | y | theta] with shard_stride between the blocks); no particle is copied to the host.  A sharded rank scores its own
+ *               shard.
+ * m is 1 .. 65536 and n_beams at most 4096.  No per-ray output exists unless classes_out is given, so pfslam_cast's cap of 2^24 rays
+ * applies only then.
+ * Refused (non-zero, pfslam_last_error names the cause under this function's name, outputs untouched, the handle goes on), in this
+ * order: a NULL handle, cast, opts or rows_out; m out of range; n_beams > 4096; source outside 0 .. 1; source 0 with poses == NULL and
+ * m != 1; source 1 with poses != NULL or m != n_particles; classes_out with more than 2^24 rays; everything pfslam_cast refuses in its
+ * options; tol, clip, z_min, z_max, count_miss or reserved_ out of range; qcap out of range; no map; the raster above 2^28 cells.  A
+ * pose that is not finite is not refused: all of its rays miss.
+ * Method.  The raster is built as for pfslam_cast (with its one extra wait).  Then one lane per ray, adjacent lanes the adjacent beams of
+ * one pose, the walk the cast's own function.  The poses come through three pointers and a stride, so one kernel reads a list (stride 3)
+ * and the particle block (stride 1).  A lane holds the seven counters of its beam and its hit; a wave adds them up by pose with a
+ * segmented reduction across its lanes, and the first lane of each pose in the wave adds what is not zero to the pose's row, which the
+ * call cleared.  On the device the row's last word is the pose's hits; the host sums them into stats[1] and writes the cost there, so no
+ * address is shared between poses: only the waves of one pose add to its row.  Class bytes are written only when asked for.  The other
+ * layout -- one 256-thread workgroup per pose, the beams strided over its threads, the row stored and neither cleared nor added to -- was
+ * built and measured first and lost at every size (2.3 x at one pose): profiles/cast_score.txt.
+ * Like pfslam_cast it first books the frames in flight and then runs on the handle's stream.  It reads the map, the scan and (source 1)
+ * the pose block, and writes no state another entry point reads.  It reuses the cast's raster buffers and pose list; its scan copy, its
+ * rows and its class bytes are buffers of its own on the handle, allocated on first use, grown when a call needs more, freed by
+ * pfslam_destroy.  Beyond the raster's wait it makes one wait, for the rows, the state words and (when asked for) the classes. */
+typedef struct pfslam_cast_score_opts {
+    float   tol;
+    float   clip;
+    float   z_min, z_max;
+    int32_t count_miss;
+    int32_t source;
+    int32_t reserved_[2];
+} pfslam_cast_score_opts;
+/* {0.1f, 1.0f, 0.1f, 20.0f, 1, 0, {0, 0}} */
+void pfslam_cast_score_default_opts(pfslam_cast_score_opts *o);
+int pfslam_cast_score(pfslam_handle *h, const float *poses /* m x 3, or NULL (see source) */, int m,
+                      const float *scan_host /* n_beams; NULL = the handle's scan */, const pfslam_cast_opts *cast,
+                      const pfslam_cast_score_opts *opts, int32_t *rows_out /* m x 8 */, uint8_t *classes_out /* NULL or m x n_beams */,
+                      int *best /* may be NULL */, int64_t stats[8] /* may be NULL */);
 /* ---- round-5 frame loop: test and measurement support (no reference counterpart) ----
  * pfslam_set_serial(h, 1): every launch of every frame on ONE stream, in the order the four chains of a frame are enqueued (what the
  * environment variable PFSLAM_SERIAL=1 sets at creation).  Results and the cell rows' bookkeeping are the same as with the chains on their
