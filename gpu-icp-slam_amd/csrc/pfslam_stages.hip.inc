@@ -1,5 +1,6 @@
 // pfslam_stages.hip.inc -- measurement reduce + weights, ICP, point-cloud map update, resample,
 // 2-D grid path and the whole step.  Included by pfslam_hip.hip (same translation unit).
+// tests/kernel_text.py cuts the text between each pair of ...-KERNEL-TEXT marks out; the kernel-text tests run it on the CPU.
 
 // ------------------------------------------------------------------------------------------
 // wave / block helpers (wave64)
@@ -20,6 +21,7 @@ __device__ __forceinline__ float wave_max_f32(float v)
 // Canonical reduction order standing in for thrust::reduce (whose order is unspecified):
 // lane l accumulates elements l, l+64, ... in ascending order, then an xor butterfly
 // 32,16,...,1.  Every lane returns the same bits.  Used for n <= 4096 (one tile).
+// WAVE-SUM-KERNEL-TEXT-BEGIN
 template <typename F>
 __device__ __forceinline__ float wave_sum_canonical(int n, F elem)
 {
@@ -30,6 +32,7 @@ __device__ __forceinline__ float wave_sum_canonical(int n, F elem)
     return acc;
 }
 
+// WAVE-SUM-KERNEL-TEXT-END
 // float <-> order-preserving signed int (so that int64 MAX all-reduces implement min/max/argmax)
 __device__ __forceinline__ int f32_to_ordered(float f)
 {
@@ -343,6 +346,7 @@ __global__ __launch_bounds__(256) void k_theta_gmax(const float *__restrict__ gp
 // ------------------------------------------------------------------------------------------
 // A9: 3x3 SVD of McAdams et al. with the operation order of the reference's svd3.h:52-401
 // ------------------------------------------------------------------------------------------
+// SVD3-KERNEL-TEXT-BEGIN
 namespace pf {
 struct Sym3 { float s11, s21, s22, s31, s32, s33; };
 
@@ -475,6 +479,7 @@ PF_HD void svd3(const float *A, float *U, float *Sg, float *V)
 }
 } // namespace pf
 
+// SVD3-KERNEL-TEXT-END
 // ------------------------------------------------------------------------------------------
 // A7/A8: kernGetWallsKD (kernel.cu:974-991) + findCorrespondenceKD (kernel.cu:874-922), fused.
 // Target cloud at the PREVIOUS robot pose; out-of-range slots are zero (H2) and still matched.
@@ -2372,6 +2377,7 @@ extern "C" int pfslam_resample(pfslam_handle *h, int frame, int *resampled, floa
 //   part[q * nt + t], q = 0 w, 1 w*w, 2 w*x, 3 w*y, 4 w*theta (pass A), 5 .. 10 xx, xy, xtheta, yy, ytheta, thetatheta (pass B)
 // Particle g of the rank-major buffers: weight gw[g]; pose in block g / stride at g % stride ([x | y | theta], stride floats each).
 // ------------------------------------------------------------------------------------------
+// ESTIMATE-DEVICE-KERNEL-TEXT-BEGIN
 #define PF_EST_WAVES 6
 __device__ __forceinline__ void est_stage(float (*s)[PF_SUM_TILE], const float *gw, const float *gpose, int stride, int g0, int cnt)
 {
@@ -2433,6 +2439,8 @@ __device__ __forceinline__ void est_finish(const float *part, int nt, int gn, fl
     out[12] = (float)gn;
     out[13] = out[14] = out[15] = 0.0f;
 }
+// ESTIMATE-DEVICE-KERNEL-TEXT-END
+// ESTIMATE-KERNEL-TEXT-BEGIN
 __global__ __launch_bounds__(PF_EST_WAVES * 64) void k_estimate_moments(const float *__restrict__ gw, const float *__restrict__ gpose,
                                                                         int stride, int gn, float *__restrict__ part, int nt)
 {
@@ -2476,6 +2484,7 @@ __global__ __launch_bounds__(PF_EST_WAVES * 64) void k_estimate_small(const floa
     est_finish(part, 1, gn, out);
 }
 
+// ESTIMATE-KERNEL-TEXT-END
 extern "C" int pfslam_estimate(pfslam_handle *h, float out[16])
 {
     if (!h || !out) return fail("pfslam_estimate: bad argument");

@@ -1,95 +1,11 @@
-// The text of the pfslam_search_best kernels (csrc/pfslam_search_best.hip.inc, cut out by tests/test_search_best_kernel_text.py into
-// search_best_kernel_text.inc behind the text of csrc/pfslam_search_wide.hip.inc, csrc/pfslam_search.hip.inc and csrc/pfslam_register.hip.inc it
-// reuses) run on the CPU behind the SIMT shim of tests/search_emu.cpp: one std::thread per GPU thread of a workgroup that has barriers or
-// shuffles, the workgroups of a launch one after the other, every buffer at the exact size pfslam_search_best requests so that a sanitizer
-// build sees any overrun.  The host's part (the descent in batches, the threshold between a batch's scoring and its expansion, the
-// compaction, the sort and the rows) is restated below, statement for statement.
-// TEST INFRASTRUCTURE, not product code.
-#include <algorithm>
-#include <barrier>
-#include <climits>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <thread>
-#include <vector>
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __global__
-#define __launch_bounds__(x)
-#define __restrict__
-#define __shared__ static
-static float *g_dyn_lds;
-#define HIP_DYNAMIC_SHARED(type, var) type *var = (type *)g_dyn_lds;
-using std::min; using std::max;
-struct uint4 { uint32_t x, y, z, w; };
-struct float4 { float x, y, z, w; };
-struct int2 { int x, y; };
-inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
-inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
-inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-inline float __int_as_float(int u) { float f; memcpy(&f, &u, 4); return f; }
-inline int __float_as_int(float f) { int u; memcpy(&u, &f, 4); return u; }
-inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-inline int __ffsll(long long v) { return __builtin_ffsll(v); }
-#define __builtin_amdgcn_read_exec() (~0ull)
-#define __builtin_amdgcn_ballot_w64(p) ((p) ? 1ull : 0ull)
-#define __builtin_amdgcn_readfirstlane(v) (v)
-struct Idx { int x; };
-static thread_local Idx threadIdx;
-static Idx blockIdx;
-static std::barrier<> *g_block;
-static std::vector<std::unique_ptr<std::barrier<>>> g_wave;
-static unsigned long long g_sh[16][64];
-inline void __syncthreads() { g_block->arrive_and_wait(); }
-template <typename T> inline T __shfl_xor(T v, int off, int) {
-    static_assert(sizeof(T) <= 8, "shuffle payload");
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    memcpy(&g_sh[w][l], &v, sizeof(T)); g_wave[w]->arrive_and_wait();
-    T r; memcpy(&r, &g_sh[w][l ^ off], sizeof(T)); g_wave[w]->arrive_and_wait();
-    return r;
-}
-inline void atomicAdd(unsigned long long *p, unsigned long long v) { __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-inline int atomicAdd(int *p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-inline int atomicMax(int *p, int v) {
-    int old = __atomic_load_n(p, __ATOMIC_RELAXED);
-    while (old < v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-    return old;
-}
-inline unsigned long long atomicMin(unsigned long long *p, unsigned long long v) {
-    unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
-    while (old > v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-    return old;
-}
-#include "register_defines.inc"   // PF_LIDAR_RANGE, PF_SVD_EPSILON: the lines of csrc/pfslam_hip.hip
-#include "pf_math.h"
-#include "kd_device.h"
-namespace pf {                    // kd_device.h only declares these outside a device compilation
-kd_rsrc_t kd_rsrc(const void *base) { return kd_rsrc_t{base}; }
-uint4 kd_load_hot(kd_rsrc_t r, int idx) { return ((const uint4 *)r.base)[idx]; }
-int kd_load_i32(kd_rsrc_t r, int idx) { return ((const int *)r.base)[idx]; }
-int kd_load_i32_bytes(kd_rsrc_t r, int byte_offset) { return ((const int *)r.base)[byte_offset / 4]; }
-uint4 kd_load_hot_at(kd_rsrc_t r, int base, int imm) { return ((const uint4 *)r.base)[(base + imm) / 16]; }
-}
-#include "search_best_kernel_text.inc"
+// The text of the pfslam_search_best kernels (csrc/pfslam_search_best.hip.inc behind the text of csrc/pfslam_search_wide.hip.inc,
+// csrc/pfslam_search.hip.inc and csrc/pfslam_register.hip.inc it reuses, cut out by tests/test_search_best_kernel_text.py) run on the CPU
+// behind tests/simt_shim.h, every buffer at the exact size pfslam_search_best requests so that a sanitizer build sees any overrun.  The
+// host's part (the descent in batches, the threshold between a batch's scoring and its expansion, the compaction, the sort and the rows)
+// is restated below, statement for statement.  TEST INFRASTRUCTURE, not product code.
+#include "simt_shim.h"
+#include "kernel_text.inc"
 
-template <typename K> void launch_block(int nthreads, K k) {
-    std::barrier<> blk(nthreads); g_block = &blk;
-    g_wave.clear();
-    for (int w = 0; w < (nthreads + 63) / 64; w++) g_wave.emplace_back(new std::barrier<>(64));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nthreads; t++) th.emplace_back([&, t] { threadIdx.x = t; k(); });
-    for (auto &x : th) x.join();
-}
-template <typename T> static std::vector<T> rd(FILE *f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "short input\n"); exit(2); }
-    return v;
-}
 // usage: search_best_emu IN.bin OUT.bin
 //   IN  = int32 {n_nodes, planar, nb, trig, half_x, half_y, half_theta, stride, frontier nodes, count, tile_log2, group_theta},
 //         float {cx, cy, ct, step_theta, max_dist, res, 0, 0}, hot[n] (16 B), z[n], parent[n], w[n], scan[nb]
@@ -139,26 +55,11 @@ int main(int argc, char **argv) {
     int *box = (int *)(state.data() + 1);
     int *count = (int *)(state.data() + 3);
     float *rows = (float *)(state.data() + 4 + 64);
-    for (int a = 0; a < na; a++) {
-        blockIdx.x = a;
-        launch_block(256, [&] { k_search_ends(scan.data(), p, trig, ends.data(), nin.data(), box); });
-    }
+    launch_threads((int)na, 256, [&] { k_search_ends(scan.data(), p, trig, ends.data(), nin.data(), box); });
     const int cell_blocks = (p.cap + 255) / 256;
-    for (int b = 0; b < cell_blocks; b++) { // (no barrier, no shuffle: the threads of a workgroup one after the other)
-        blockIdx.x = b;
-        for (int t = 0; t < 256; t++) {
-            threadIdx.x = t;
-            k_search_field(tree, p, box, field.data());
-        }
-    }
+    launch_serial(cell_blocks, 256, [&] { k_search_field(tree, p, box, field.data()); }); // (no barrier, no shuffle: the threads of a workgroup one after the other)
     for (int L = 1; L <= top; L++)
-        for (int b = 0; b < cell_blocks; b++) {
-            blockIdx.x = b;
-            for (int t = 0; t < 256; t++) {
-                threadIdx.x = t;
-                k_wide_pyramid(box, p, (1 << (L - 1)) * p.stride, field.data() + level * (size_t)(L - 1), field.data() + level * (size_t)L);
-            }
-        }
+        launch_serial(cell_blocks, 256, [&] { k_wide_pyramid(box, p, (1 << (L - 1)) * p.stride, field.data() + level * (size_t)(L - 1), field.data() + level * (size_t)L); });
     long long have[PF_WIDE_MAX_LEVEL + 1] = {0}, done[PF_WIDE_MAX_LEVEL + 1] = {0};
     long long bounded = 0, scored = 0, batches = 0;
     have[top] = n_top;
@@ -171,13 +72,7 @@ int main(int argc, char **argv) {
         const int n = (int)std::min<long long>(have[L] - done[L], L ? std::max(room / 4, 1) : room);
         int *nodes = nodes_buf.data() + (size_t)room * (size_t)L;
         if (L == top) {
-            for (int b = 0; b < (n + 255) / 256; b++) {
-                blockIdx.x = b;
-                for (int t = 0; t < 256; t++) {
-                    threadIdx.x = t;
-                    k_wide_top(p, L, done[L], n, nodes);
-                }
-            }
+            launch_serial((n + 255) / 256, 256, [&] { k_wide_top(p, L, done[L], n, nodes); });
         } else {
             nodes += done[L];
         }
@@ -185,19 +80,12 @@ int main(int argc, char **argv) {
         batches++;
         (L ? bounded : scored) += n;
         const uint16_t *fL = field.data() + level * (size_t)L;
-        for (int b = 0; b < n; b++) {
-            blockIdx.x = b;
-            if (L) launch_block(64, [&] { k_best_score<false>(nodes, ends.data(), nin.data(), box, field.data(), fL, p, q, lb.data(), tab.data()); });
-            else launch_block(64, [&] { k_best_score<true>(nodes, ends.data(), nin.data(), box, field.data(), fL, p, q, lb.data(), tab.data()); });
-        }
+        if (L) launch_threads(n, 64, [&] { k_best_score<false>(nodes, ends.data(), nin.data(), box, field.data(), fL, p, q, lb.data(), tab.data()); });
+        else launch_threads(n, 64, [&] { k_best_score<true>(nodes, ends.data(), nin.data(), box, field.data(), fL, p, q, lb.data(), tab.data()); });
         if (L == 0) continue;
         *count = 0;
-        blockIdx.x = 0;
-        launch_block(256, [&] { k_best_thr(tab.data() + cells, want, thr); });
-        for (int b = 0; b < (n + 255) / 256; b++) {
-            blockIdx.x = b;
-            launch_block(256, [&] { k_best_expand(nodes, lb.data(), n, L, p, q, thr, tab.data(), nodes_buf.data() + (size_t)room * (size_t)(L - 1), count); });
-        }
+        launch_threads(1, 256, [&] { k_best_thr(tab.data() + cells, want, thr); });
+        launch_threads((n + 255) / 256, 256, [&] { k_best_expand(nodes, lb.data(), n, L, p, q, thr, tab.data(), nodes_buf.data() + (size_t)room * (size_t)(L - 1), count); });
         const int kids = *count;
         if (kids < 0 || kids > 4 * n) return 8;
         if (kids) {
@@ -206,26 +94,15 @@ int main(int argc, char **argv) {
             done[L] = 0;
         }
     }
-    blockIdx.x = 0;
-    launch_block(256, [&] { k_best_thr(tab.data() + cells, want, thr); });
-    for (int b = 0; b < (int)((cells + 255) / 256); b++) {
-        blockIdx.x = b;
-        for (int t = 0; t < 256; t++) {
-            threadIdx.x = t;
-            k_best_compact(tab.data(), (int)cells, thr, list.data());
-        }
-    }
+    launch_threads(1, 256, [&] { k_best_thr(tab.data() + cells, want, thr); });
+    launch_serial((int)((cells + 255) / 256), 256, [&] { k_best_compact(tab.data(), (int)cells, thr, list.data()); });
     const long long n_list = (long long)(list[0] & 0xffffffffull);
     if (n_list > cells) return 10;
     const int n_rows = (int)std::min<long long>(n_list, want);
     std::partial_sort(list.begin() + 1, list.begin() + 1 + n_rows, list.begin() + 1 + n_list);
     if (n_rows) {
         memcpy(keys, list.data() + 1, (size_t)n_rows * 8);
-        blockIdx.x = 0;
-        for (int t = 0; t < 64; t++) {
-            threadIdx.x = t;
-            k_best_rows(keys, n_rows, nin.data(), p, rows);
-        }
+        launch_serial(1, 64, [&] { k_best_rows(keys, n_rows, nin.data(), p, rows); });
     }
     const SearchBox B = search_box(box, p);
     const long long found = n_rows;

@@ -1,95 +1,10 @@
-// The text of the pfslam_search kernels (csrc/pfslam_search.hip.inc, cut out by tests/test_search_kernel_text.py into search_kernel_text.inc
-// behind the text of csrc/pfslam_register.hip.inc it reuses) run on the CPU behind a small SIMT shim: one std::thread per GPU thread of a
-// workgroup that has barriers or shuffles (k_search_ends, k_search_score), a std::barrier per workgroup for __syncthreads and one per wave
-// for __shfl_xor, static LDS as function-local statics, every buffer at the exact size pfslam_search requests so that a sanitizer build sees
-// any overrun.  The workgroups of a launch run one after the other; the threads of k_search_field, which meet nowhere, do too.  What the
-// kernels reuse is compiled from the product's own files, unchanged: csrc/pf_math.h and csrc/kd_device.h whole (behind an empty
-// <hip/hip_runtime.h> the test provides) and the cut text of pf::kd_nearest_exact.  kd_device.h needs clang (ext_vector_type).
-// TEST INFRASTRUCTURE, not product code.
-#include <algorithm>
-#include <barrier>
-#include <climits>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <thread>
-#include <vector>
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __global__
-#define __launch_bounds__(x)
-#define __restrict__
-#define __shared__ static
-static float *g_dyn_lds;
-#define HIP_DYNAMIC_SHARED(type, var) type *var = (type *)g_dyn_lds;
-using std::min; using std::max;
-struct uint4 { uint32_t x, y, z, w; };
-struct float4 { float x, y, z, w; };
-struct int2 { int x, y; };
-inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
-inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
-inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-inline float __int_as_float(int u) { float f; memcpy(&f, &u, 4); return f; }
-inline int __float_as_int(float f) { int u; memcpy(&u, &f, 4); return u; }
-inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-inline int __ffsll(long long v) { return __builtin_ffsll(v); }
-#define __builtin_amdgcn_read_exec() (~0ull)
-#define __builtin_amdgcn_ballot_w64(p) ((p) ? 1ull : 0ull)
-#define __builtin_amdgcn_readfirstlane(v) (v)
-struct Idx { int x; };
-static thread_local Idx threadIdx;
-static Idx blockIdx;
-static std::barrier<> *g_block;
-static std::vector<std::unique_ptr<std::barrier<>>> g_wave;
-static unsigned long long g_sh[16][64];
-inline void __syncthreads() { g_block->arrive_and_wait(); }
-template <typename T> inline T __shfl_xor(T v, int off, int) {
-    static_assert(sizeof(T) <= 8, "shuffle payload");
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    memcpy(&g_sh[w][l], &v, sizeof(T)); g_wave[w]->arrive_and_wait();
-    T r; memcpy(&r, &g_sh[w][l ^ off], sizeof(T)); g_wave[w]->arrive_and_wait();
-    return r;
-}
-inline void atomicAdd(unsigned long long *p, unsigned long long v) { __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-inline int atomicMax(int *p, int v) {
-    int old = __atomic_load_n(p, __ATOMIC_RELAXED);
-    while (old < v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-    return old;
-}
-inline unsigned long long atomicMin(unsigned long long *p, unsigned long long v) {
-    unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
-    while (old > v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-    return old;
-}
-#include "register_defines.inc"   // PF_LIDAR_RANGE, PF_SVD_EPSILON: the lines of csrc/pfslam_hip.hip
-#include "pf_math.h"
-#include "kd_device.h"
-namespace pf {                    // kd_device.h only declares these outside a device compilation
-kd_rsrc_t kd_rsrc(const void *base) { return kd_rsrc_t{base}; }
-uint4 kd_load_hot(kd_rsrc_t r, int idx) { return ((const uint4 *)r.base)[idx]; }
-int kd_load_i32(kd_rsrc_t r, int idx) { return ((const int *)r.base)[idx]; }
-int kd_load_i32_bytes(kd_rsrc_t r, int byte_offset) { return ((const int *)r.base)[byte_offset / 4]; }
-uint4 kd_load_hot_at(kd_rsrc_t r, int base, int imm) { return ((const uint4 *)r.base)[(base + imm) / 16]; }
-}
-#include "search_kernel_text.inc"
+// The text of the pfslam_search kernels (csrc/pfslam_search.hip.inc behind the text of csrc/pfslam_register.hip.inc it reuses, cut out by
+// tests/test_search_kernel_text.py) run on the CPU behind tests/simt_shim.h: k_search_ends and k_search_score, which have barriers or
+// shuffles, a thread per GPU thread; k_search_field, whose threads meet nowhere, one thread after the other.  Every buffer has exactly the
+// size pfslam_search requests, so that a sanitizer build sees any overrun.  TEST INFRASTRUCTURE, not product code.
+#include "simt_shim.h"
+#include "kernel_text.inc"
 
-template <typename K> void launch_block(int nthreads, K k) {
-    std::barrier<> blk(nthreads); g_block = &blk;
-    g_wave.clear();
-    for (int w = 0; w < (nthreads + 63) / 64; w++) g_wave.emplace_back(new std::barrier<>(64));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nthreads; t++) th.emplace_back([&, t] { threadIdx.x = t; k(); });
-    for (auto &x : th) x.join();
-}
-template <typename T> static std::vector<T> rd(FILE *f, size_t n) {
-    std::vector<T> v(n);
-    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "short input\n"); exit(2); }
-    return v;
-}
 // usage: search_emu IN.bin OUT.bin
 //   IN  = int32 {n_nodes, planar, nb, trig, half_x, half_y, half_theta, stride}, float {cx, cy, ct, step_theta, max_dist, res, 0, 0},
 //         hot[n] (16 B), z[n], parent[n], w[n], scan[nb]
@@ -124,25 +39,11 @@ int main(int argc, char **argv) {
     unsigned long long *key = state;
     int *box = (int *)(state + 1);
     std::vector<float> out(PF_SEARCH_OUT, -1.0f);
-    for (int a = 0; a < na; a++) {
-        blockIdx.x = a;
-        launch_block(256, [&] { k_search_ends(scan.data(), p, trig, ends.data(), nin.data(), box); });
-    }
-    for (int b = 0; b < (p.cap + 255) / 256; b++) { // (no barrier, no shuffle: the threads of a workgroup one after the other)
-        blockIdx.x = b;
-        for (int t = 0; t < 256; t++) {
-            threadIdx.x = t;
-            k_search_field(tree, p, box, field.data());
-        }
-    }
+    launch_threads(na, 256, [&] { k_search_ends(scan.data(), p, trig, ends.data(), nin.data(), box); });
+    launch_serial((p.cap + 255) / 256, 256, [&] { k_search_field(tree, p, box, field.data()); }); // (no barrier, no shuffle: the threads of a workgroup one after the other)
     const int chunks = (nx * ny + 63) / 64;
-    for (int b = 0; b < na * chunks; b++) {
-        blockIdx.x = b;
-        launch_block(64, [&] { k_search_score(ends.data(), nin.data(), box, field.data(), p, chunks, scores.data(), key); });
-    }
-    blockIdx.x = 0;
-    threadIdx.x = 0;
-    k_search_result(key, nin.data(), p, out.data());
+    launch_threads(na * chunks, 64, [&] { k_search_score(ends.data(), nin.data(), box, field.data(), p, chunks, scores.data(), key); });
+    launch_serial(1, 1, [&] { k_search_result(key, nin.data(), p, out.data()); });
     const SearchBox B = search_box(box, p);
     const int dims[4] = {B.W, B.H, 0, 0};
     f = fopen(argv[2], "wb");

@@ -5,18 +5,14 @@ Ranges, cells, stats and the raster must be the restatement's (tests/cast_ref.py
 jumps: into the box, out of empty tiles) and for the plain walk it is measured against (every cell tested), which shows that a jump
 never passes an occupied cell and that no index leaves the tiles.  What it cannot show is the GPU's arithmetic and its atomics:
 tests/test_gpu_cast.py does."""
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import cast_ref as CR
-from test_register_kernel_text import clangxx
+import kernel_text as KT
+from kernel_text import poses_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gpu-icp-slam_amd", "csrc")
 RES = (0.025, 0.025)
 
 
@@ -27,26 +23,7 @@ def pts(pkg):
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    cxx = clangxx()
-    if cxx is None:
-        pytest.fail("clang++ is needed to compile the kernel text for the CPU")
-    d = tmp_path_factory.mktemp("cast_emu")
-    src = open(os.path.join(CSRC, "pfslam_cast.hip.inc")).read()
-    first, last = "// CAST-KERNEL-TEXT-BEGIN", "// CAST-KERNEL-TEXT-END"
-    assert src.count(first) == 1 and src.count(last) == 1, "the kernel text has moved"
-    text = src[src.index(first):src.index(last)]
-    for name in ("k_cast_box", "k_cast_splat", "k_cast_count", "k_cast_rays", "k_cast_expand"):
-        assert name in text
-    (d / "cast_kernel_text.inc").write_text(text)
-    os.makedirs(str(d / "hip"))
-    (d / "hip" / "hip_runtime.h").write_text("// (the shim of cast_emu.cpp stands in for the HIP runtime's declarations)\n")
-    for name in ("pf_math.h", "kd_device.h"):
-        shutil.copy(os.path.join(CSRC, name), str(d / name))
-    shutil.copy(os.path.join(ROOT, "tests", "cast_emu.cpp"), str(d / "cast_emu.cpp"))
-    exe = str(d / "cast_emu")
-    subprocess.check_call([cxx, "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-Wno-unknown-attributes", "-pthread", "-I", str(d), str(d / "cast_emu.cpp"), "-o", exe])
-    return d, exe
+    return KT.build(tmp_path_factory, "cast", ("k_cast_box", "k_cast_splat", "k_cast_count", "k_cast_rays", "k_cast_expand"))
 
 
 def run_emu(emu, tag, nodes, poses, nb, res=RES, **opts):
@@ -61,8 +38,7 @@ def run_emu(emu, tag, nodes, poses, nb, res=RES, **opts):
         f.write(np.array([res[0], res[1], o["max_range"], o["w_min"], o["no_hit"], 0, 0, 0], np.float32).tobytes())
         f.write(nodes.tobytes())
         f.write(poses.tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    KT.run(exe, fin, fout)
     raw = open(fout, "rb").read()
     stats = np.frombuffer(raw, np.int64, 8)
     rays = m * nb
@@ -84,14 +60,6 @@ def check(emu, tag, nodes, poses, nb, res=RES, **opts):
         assert CR.same(got, want) is None, "%s walk: %s" % (walk, CR.same(got, want))
         assert got["occ"].shape == ras.dense().shape and (got["occ"] == ras.dense()).all(), "the raster differs"
     return want
-
-
-def poses_of(m, seed=3):
-    """m poses inside the 40 m map, the first the one the other tests cast from."""
-    rng = np.random.RandomState(seed)
-    p = np.concatenate([rng.uniform(-15, 15, (m, 2)), rng.uniform(-3.2, 3.2, (m, 1))], axis=1).astype(np.float32)
-    p[0] = (0.5, 0.3, 0.1)
-    return p
 
 
 @pytest.mark.parametrize("nb,m", [(1, 1), (65, 3), (1081, 1), (65, 65)])

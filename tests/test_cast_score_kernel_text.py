@@ -5,20 +5,15 @@ AddressSanitizer and UBSan, every buffer at exactly the size the entry point req
 (tests/cast_score_ref.py), bit for bit -- for the walk the library runs and for the plain walk, for the pose list (x, y, theta rows) and
 for the particle block (three arrays with a stride between them).  What it cannot show is the GPU's arithmetic, its shuffles and its
 atomics: tests/test_gpu_cast_score.py does."""
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import cast_ref as CR
 import cast_score_ref as SR
-from test_cast_kernel_text import poses_of
-from test_register_kernel_text import clangxx
+import kernel_text as KT
+from kernel_text import poses_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gpu-icp-slam_amd", "csrc")
 RES = (0.025, 0.025)
 
 
@@ -28,34 +23,12 @@ def world(pkg):
     return pts, pkg.synth.make_scan(segs, (0.5, 0.3, 0.1), noise=0).astype(np.float32)
 
 
-def cut(name, first, last, kernels):
-    src = open(os.path.join(CSRC, name)).read()
-    assert src.count(first) == 1 and src.count(last) == 1, "the kernel text has moved"
-    text = src[src.index(first):src.index(last)]
-    for k in kernels:
-        assert k in text
-    return text
-
-
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    cxx = clangxx()
-    if cxx is None:
-        pytest.fail("clang++ is needed to compile the kernel text for the CPU")
-    d = tmp_path_factory.mktemp("cast_score_emu")
-    (d / "cast_kernel_text.inc").write_text(cut("pfslam_cast.hip.inc", "// CAST-KERNEL-TEXT-BEGIN", "// CAST-KERNEL-TEXT-END",
-                                                ("k_cast_box", "k_cast_splat", "k_cast_count", "cast_walk", "k_cast_rays")))
-    (d / "cast_score_kernel_text.inc").write_text(cut("pfslam_cast_score.hip.inc", "// CAST-SCORE-KERNEL-TEXT-BEGIN", "// CAST-SCORE-KERNEL-TEXT-END",
-                                                      ("k_cast_score", "cast_walk<SKIP>")))
-    os.makedirs(str(d / "hip"))
-    (d / "hip" / "hip_runtime.h").write_text("// (the shim of cast_score_emu.cpp stands in for the HIP runtime's declarations)\n")
-    for name in ("pf_math.h", "kd_device.h"):
-        shutil.copy(os.path.join(CSRC, name), str(d / name))
-    shutil.copy(os.path.join(ROOT, "tests", "cast_score_emu.cpp"), str(d / "cast_score_emu.cpp"))
-    exe = str(d / "cast_score_emu")
-    subprocess.check_call([cxx, "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-Wno-unknown-attributes", "-pthread", "-I", str(d), str(d / "cast_score_emu.cpp"), "-o", exe])
-    return d, exe
+    for sec, names in (("cast", ("k_cast_box", "k_cast_splat", "k_cast_count", "cast_walk", "k_cast_rays")), ("cast_score", ("k_cast_score", "cast_walk<SKIP>"))):
+        for name in names:                                      # (each in its own section: either text names the other's functions too)
+            assert name in KT.section(sec)
+    return KT.build(tmp_path_factory, "cast_score", ())
 
 
 def run_emu(emu, tag, nodes, poses, scan, nb, res=RES, soa=0, classes=True, cast=None, **opts):
@@ -78,8 +51,7 @@ def run_emu(emu, tag, nodes, poses, scan, nb, res=RES, soa=0, classes=True, cast
         f.write(nodes.tobytes())
         f.write(np.ascontiguousarray(block).tobytes())
         f.write(np.ascontiguousarray(scan, np.float32).tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    KT.run(exe, fin, fout)
     raw = open(fout, "rb").read()
     rays = m * nb
     one = 64 + 32 * m + (rays if classes else 0)

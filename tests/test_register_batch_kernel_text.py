@@ -6,21 +6,16 @@ other) as a stand-alone program with -ffp-contract=off like the library, under A
 restatement's register (tests/register_ref.py) bit for bit: pose, status, iterations, pairs, residual -- with either workgroup size the
 host may pick -- which also shows that no index leaves the LDS buffer or a result row and that every thread reaches every barrier, in
 rows that stop early too.  What it cannot show is the GPU's arithmetic and memory model: tests/test_gpu_register_batch.py does."""
-import os
-import re
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import kernel_text as KT
+from kernel_text import device_arrays
 import register_batch_ref as B
 import register_ref as R
-from test_register_kernel_text import clangxx, device_arrays
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gpu-icp-slam_amd", "csrc")
 START = np.array([0.6, 0.22, 0.13], np.float32)
 # (map, beams, rows, threads, options)
 CASES = [("p4000", 1, 3, 1024, dict(max_iters=3, min_pairs=1, max_dist=0.0)), ("p4000", 65, 3, 256, dict(max_iters=3)), ("p4000", 65, 3, 1024, dict(max_iters=2)),
@@ -44,35 +39,7 @@ def maps(pkg):
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    cxx = clangxx()
-    if cxx is None:
-        pytest.fail("clang++ is needed to compile the kernel text for the CPU")
-    d = tmp_path_factory.mktemp("register_batch_emu")
-    stages = open(os.path.join(CSRC, "pfslam_stages.hip.inc")).read()
-    reg = open(os.path.join(CSRC, "pfslam_register.hip.inc")).read()
-    batch = open(os.path.join(CSRC, "pfslam_register_batch.hip.inc")).read()
-    main = open(os.path.join(CSRC, "pfslam_hip.hip")).read()
-    cuts = [(stages, "template <typename F>\n__device__ __forceinline__ float wave_sum_canonical", "// float <-> order-preserving signed int"),
-            (stages, "namespace pf {\nstruct Sym3", "// ------------------------------------------------------------------------------------------\n// A7/A8"),
-            (reg, "// REGISTER-KERNEL-TEXT-BEGIN", "// REGISTER-KERNEL-TEXT-END"),
-            (batch, "// REGISTER-BATCH-KERNEL-TEXT-BEGIN", "// REGISTER-BATCH-KERNEL-TEXT-END")]
-    text = ""
-    for src, first, last in cuts:
-        assert src.count(first) == 1 and src.count(last) == 1, "the kernel text has moved: %r" % first
-        text += src[src.index(first):src.index(last, src.index(first))]
-    assert "k_register_batch" in text and "HIP_DYNAMIC_SHARED" in text and "kd_nearest_exact" in text and "void svd3" in text
-    (d / "register_batch_kernel_text.inc").write_text(text)
-    defs = [re.search(r"^#define %s .*$" % name, main, re.M).group(0) for name in ("PF_LIDAR_RANGE", "PF_SVD_EPSILON")]
-    (d / "register_defines.inc").write_text("\n".join(defs) + "\n")
-    os.makedirs(str(d / "hip"))
-    (d / "hip" / "hip_runtime.h").write_text("// (the shim of register_batch_emu.cpp stands in for the HIP runtime's declarations)\n")
-    for name in ("pf_math.h", "kd_device.h"):
-        shutil.copy(os.path.join(CSRC, name), str(d / name))
-    shutil.copy(os.path.join(ROOT, "tests", "register_batch_emu.cpp"), str(d / "register_batch_emu.cpp"))
-    exe = str(d / "register_batch_emu")
-    subprocess.check_call([cxx, "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-Wno-unknown-attributes", "-pthread", "-I", str(d), str(d / "register_batch_emu.cpp"), "-o", exe])
-    return d, exe
+    return KT.build(tmp_path_factory, "register_batch", ("k_register_batch", "HIP_DYNAMIC_SHARED", "kd_nearest_exact", "void svd3"), ("PF_LIDAR_RANGE", "PF_SVD_EPSILON"))
 
 
 def run_emu(emu, tag, tree, scan, starts, threads, opts):
@@ -89,8 +56,7 @@ def run_emu(emu, tag, tree, scan, starts, threads, opts):
             f.write(np.ascontiguousarray(a).tobytes())
         f.write(struct.pack("<4i3fi", o["max_iters"], o["match"], o["select"], o["update"], o["max_dist"], o["eps_xy"], o["eps_theta"], o["min_pairs"]))
         f.write(starts.tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    KT.run(exe, fin, fout)
     out = np.fromfile(fout, np.float32).reshape(len(starts), 12)
     assert (out[:, 3] == 0).all() and (out[:, 8:] == 0).all()
     info = np.zeros((len(starts), 8), np.float32)

@@ -5,20 +5,15 @@ program with -ffp-contract=off like the library, under AddressSanitizer and UBSa
 the restatement's status, pose and trace bit for bit (tests/register_ref.py), nearest its index and d2 -- which also shows that no index
 leaves a buffer, that every thread reaches every barrier and that the stackless walk ends on every kind of tree the library holds.  What it
 cannot show is the GPU's arithmetic and memory model: tests/test_gpu_register.py does."""
-import os
-import re
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-import oracle_lib as O
+import kernel_text as KT
+from kernel_text import device_arrays
 import register_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gpu-icp-slam_amd", "csrc")
 MAPS = ("p2", "p3", "p4000", "np300", "grown4500")
 # (map, beams, match, select, update, max_iters, max_dist)
 CASES = [(m, 1081, 1, 1, 1, 4, 0.5 if m in ("p4000", "grown4500") else 0.0) for m in MAPS if m not in ("p2", "p3")]
@@ -26,41 +21,6 @@ CASES += [("p4000", nb, 1, 1, 1, 3, 0.5) for nb in (1, 64, 65, 1024, 1025, 4096)
 CASES += [("p4000", 1081, 0, 0, 0, 3, 0.5), ("grown4500", 1025, 0, 1, 1, 3, 0.5), ("np300", 65, 1, 0, 0, 3, 0.5), ("np300", 1024, 0, 1, 0, 2, 0.0),
           ("p2", 64, 0, 0, 1, 2, 0.5), ("p2", 1081, 1, 0, 0, 2, 0.5), ("p3", 1, 1, 0, 1, 2, 0.5), ("p3", 4096, 0, 0, 0, 2, 0.5),
           ("p4000", 1081, 1, 1, 1, 40, 0.5)]
-
-
-def clangxx():
-    """clang++ (kd_device.h uses ext_vector_type): the one hipcc drives, or any on the path."""
-    import importlib
-    cands = [shutil.which("clang++")]
-    try:
-        hipcc = importlib.import_module("gpu-icp-slam_amd.build").hipcc()
-        rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))
-        cands = [os.path.join(rocm, "lib", "llvm", "bin", "clang++"), os.path.join(rocm, "llvm", "bin", "clang++")] + cands
-    except Exception:
-        pass
-    for c in cands:
-        if c and os.path.exists(c):
-            return c
-    return None
-
-
-def device_arrays(tree):
-    """The four device arrays of a map as pfslam_set_map lays them out (csrc/kd_device.h): hot records, z (a planar z level's true left
-    child as int bits), parents, weights; and the planar flag."""
-    n = len(tree)
-    planar = int(not (tree["z"] != 0).any())
-    left = tree["left"].copy()
-    z = tree["z"].astype(np.float32).copy()
-    if planar:
-        zl = tree["axis"] == 2
-        z.view(np.int32)[zl] = tree["left"][zl]
-        left[zl] = tree["right"][zl]
-    hot = np.zeros((n, 4), np.uint32)
-    hot[:, 0] = tree["x"].astype(np.float32).view(np.uint32)
-    hot[:, 1] = tree["y"].astype(np.float32).view(np.uint32)
-    hot[:, 2] = (left.astype(np.int64) & 0x3fffffff).astype(np.uint32) | (tree["axis"].astype(np.uint32) << 30)
-    hot[:, 3] = tree["right"].astype(np.int32).view(np.uint32)
-    return hot, z, tree["parent"].astype(np.int32), tree["w"].astype(np.float32), planar
 
 
 @pytest.fixture(scope="module")
@@ -84,33 +44,7 @@ def _path(tree, i):
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    cxx = clangxx()
-    if cxx is None:
-        pytest.fail("clang++ is needed to compile the kernel text for the CPU")
-    d = tmp_path_factory.mktemp("register_emu")
-    stages = open(os.path.join(CSRC, "pfslam_stages.hip.inc")).read()
-    reg = open(os.path.join(CSRC, "pfslam_register.hip.inc")).read()
-    main = open(os.path.join(CSRC, "pfslam_hip.hip")).read()
-    cuts = [(stages, "template <typename F>\n__device__ __forceinline__ float wave_sum_canonical", "// float <-> order-preserving signed int"),
-            (stages, "namespace pf {\nstruct Sym3", "// ------------------------------------------------------------------------------------------\n// A7/A8"),
-            (reg, "// REGISTER-KERNEL-TEXT-BEGIN", "// REGISTER-KERNEL-TEXT-END")]
-    text = ""
-    for src, first, last in cuts:
-        assert src.count(first) == 1 and last in src, "the kernel text has moved: %r" % first
-        text += src[src.index(first):src.index(last, src.index(first))]
-    assert "k_register" in text and "kd_nearest_exact" in text and "void svd3" in text
-    (d / "register_kernel_text.inc").write_text(text)
-    defs = [re.search(r"^#define %s .*$" % name, main, re.M).group(0) for name in ("PF_LIDAR_RANGE", "PF_SVD_EPSILON")]
-    (d / "register_defines.inc").write_text("\n".join(defs) + "\n")
-    os.makedirs(str(d / "hip"))
-    (d / "hip" / "hip_runtime.h").write_text("// (the shim of register_emu.cpp stands in for the HIP runtime's declarations)\n")
-    for name in ("pf_math.h", "kd_device.h"):
-        shutil.copy(os.path.join(CSRC, name), str(d / name))
-    shutil.copy(os.path.join(ROOT, "tests", "register_emu.cpp"), str(d / "register_emu.cpp"))
-    exe = str(d / "register_emu")
-    subprocess.check_call([cxx, "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-Wno-unknown-attributes", "-pthread", "-I", str(d), str(d / "register_emu.cpp"), "-o", exe])
-    return d, exe
+    return KT.build(tmp_path_factory, "register", ("k_register", "kd_nearest_exact", "void svd3"), ("PF_LIDAR_RANGE", "PF_SVD_EPSILON"))
 
 
 def run_emu(emu, tag, tree, scan, queries, opts, start, use_start=1):
@@ -127,8 +61,7 @@ def run_emu(emu, tag, tree, scan, queries, opts, start, use_start=1):
             f.write(np.ascontiguousarray(a).tobytes())
         f.write(struct.pack("<4i3fi", o["max_iters"], o["match"], o["select"], o["update"], o["max_dist"], o["eps_xy"], o["eps_theta"], o["min_pairs"]))
         f.write(np.ascontiguousarray(start, np.float32).tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    KT.run(exe, fin, fout)
     raw = np.fromfile(fout, np.uint8)
     res = {}
     off = 0

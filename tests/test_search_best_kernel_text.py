@@ -1,28 +1,23 @@
 """The pfslam_search_best kernels' own text, run on the CPU (no GPU needed): tests/search_best_emu.cpp compiles the five kernels cut out of
 csrc/pfslam_search_best.hip.inc -- behind the text of csrc/pfslam_search_wide.hip.inc and csrc/pfslam_search.hip.inc (k_search_ends,
-k_search_field, k_wide_pyramid, k_wide_top, launched as they are) and what that text reuses, none of it changed -- behind the SIMT shim of
-tests/search_emu.cpp as a stand-alone program with -ffp-contract=off like the library, under AddressSanitizer and UBSan, every buffer at
+k_search_field, k_wide_pyramid, k_wide_top, launched as they are) and what that text reuses, none of it changed -- behind the SIMT shim
+(tests/simt_shim.h) as a stand-alone program with -ffp-contract=off like the library, under AddressSanitizer and UBSan, every buffer at
 exactly the size pfslam_search_best requests.  The rows must be the restatement's (tests/search_best_ref.py: the full volume cut into
 cells, the smallest key of each, the `count` smallest of those), bit for bit -- which also shows that no index leaves the table, the
 list, a field level or a frontier buffer, whatever the frontier's size.  The cases are those of tests/test_search_wide_kernel_text.py,
 each with count 1, 5 and 64.  What it cannot show is the GPU's arithmetic and memory model: tests/test_gpu_search_best.py does."""
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import kernel_text as KT
+from kernel_text import device_arrays
 import register_ref as R
 import search_best_ref as Bs
 import search_ref as S
 import search_wide_ref as Wd
-from test_register_kernel_text import clangxx, device_arrays
 from test_search_wide_kernel_text import CASES, CENTRE, ROOM
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gpu-icp-slam_amd", "csrc")
 # (tile_log2, group_theta) per case of CASES: one cell; two tiles; partial tiles at stride 3; tiles of one candidate under a frontier of
 # 64 nodes; groups larger than na under a frontier of 4; the defaults
 CELLS = [(3, 8), (2, 1), (2, 2), (0, 1), (1, 8), (3, 8)]
@@ -38,41 +33,8 @@ def maps(pkg):
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    cxx = clangxx()
-    if cxx is None:
-        pytest.fail("clang++ is needed to compile the kernel text for the CPU")
-    d = tmp_path_factory.mktemp("search_best_emu")
-    stages = open(os.path.join(CSRC, "pfslam_stages.hip.inc")).read()
-    reg = open(os.path.join(CSRC, "pfslam_register.hip.inc")).read()
-    srch = open(os.path.join(CSRC, "pfslam_search.hip.inc")).read()
-    wide = open(os.path.join(CSRC, "pfslam_search_wide.hip.inc")).read()
-    best = open(os.path.join(CSRC, "pfslam_search_best.hip.inc")).read()
-    main = open(os.path.join(CSRC, "pfslam_hip.hip")).read()
-    cuts = [(stages, "template <typename F>\n__device__ __forceinline__ float wave_sum_canonical", "// float <-> order-preserving signed int"),
-            (stages, "namespace pf {\nstruct Sym3", "// ------------------------------------------------------------------------------------------\n// A7/A8"),
-            (reg, "// REGISTER-KERNEL-TEXT-BEGIN", "// REGISTER-KERNEL-TEXT-END"),
-            (srch, "// SEARCH-KERNEL-TEXT-BEGIN", "// SEARCH-KERNEL-TEXT-END"),
-            (wide, "// SEARCH-WIDE-KERNEL-TEXT-BEGIN", "// SEARCH-WIDE-KERNEL-TEXT-END"),
-            (best, "// SEARCH-BEST-KERNEL-TEXT-BEGIN", "// SEARCH-BEST-KERNEL-TEXT-END")]
-    text = ""
-    for src, first, last in cuts:
-        assert src.count(first) == 1 and src.count(last) == 1, "the kernel text has moved: %r" % first
-        text += src[src.index(first):src.index(last, src.index(first))]
-    for name in ("search_derive", "k_search_ends", "k_search_field", "k_wide_pyramid", "k_wide_top", "k_best_score", "k_best_thr", "k_best_expand", "k_best_compact",
-                 "k_best_rows", "kd_nearest_exact"):
-        assert name in text
-    (d / "search_best_kernel_text.inc").write_text(text)
-    defs = [re.search(r"^#define %s .*$" % name, main, re.M).group(0) for name in ("PF_LIDAR_RANGE", "PF_SVD_EPSILON")]
-    (d / "register_defines.inc").write_text("\n".join(defs) + "\n")
-    os.makedirs(str(d / "hip"))
-    (d / "hip" / "hip_runtime.h").write_text("// (the shim of search_best_emu.cpp stands in for the HIP runtime's declarations)\n")
-    for name in ("pf_math.h", "kd_device.h"):
-        shutil.copy(os.path.join(CSRC, name), str(d / name))
-    shutil.copy(os.path.join(ROOT, "tests", "search_best_emu.cpp"), str(d / "search_best_emu.cpp"))
-    exe = str(d / "search_best_emu")
-    subprocess.check_call([cxx, "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-Wno-unknown-attributes", "-pthread", "-I", str(d), str(d / "search_best_emu.cpp"), "-o", exe])
-    return d, exe
+    return KT.build(tmp_path_factory, "search_best", ("search_derive", "k_search_ends", "k_search_field", "k_wide_pyramid", "k_wide_top", "k_best_score", "k_best_thr",
+                                                     "k_best_expand", "k_best_compact", "k_best_rows", "kd_nearest_exact"), ("PF_LIDAR_RANGE", "PF_SVD_EPSILON"))
 
 
 def run_emu(emu, tag, tree, scan, centre, opts, count, ls, g, room=ROOM, res=0.025):
@@ -87,8 +49,7 @@ def run_emu(emu, tag, tree, scan, centre, opts, count, ls, g, room=ROOM, res=0.0
         f.write(np.array([centre[0], centre[1], centre[2], o["step_theta"], o["max_dist"], res, 0, 0], np.float32).tobytes())
         for a in (hot, z, parent, w, scan):
             f.write(np.ascontiguousarray(a).tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    KT.run(exe, fin, fout)
     raw = np.fromfile(fout, np.uint8)
     found = int(raw[:8].view(np.int64)[0])
     assert 0 <= found <= count and len(raw) == 72 + found * (8 + 48)

@@ -6,22 +6,16 @@ every buffer at exactly the size the entry point requests.  The call is pfslam_s
 search's, and cov_out the restatement's (tests/search_cov_ref.py), bit for bit -- which also shows that the stepped index (a, j, i) is
 the divided one, that no index leaves a buffer and that every thread reaches every barrier.  What it cannot show is the GPU's arithmetic
 and memory model: tests/test_gpu_search_cov.py does."""
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import kernel_text as KT
 import register_ref as R
 import search_cov_ref as SC
 import search_ref as S
 import search_scan_ref as SS
-from test_register_kernel_text import clangxx
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gpu-icp-slam_amd", "csrc")
 REF_POSE = np.array([0.5, 0.3, 0.1], np.float32)       # where the reference scan is cast from
 POSE = (0.58, 0.24, 0.125)                             # where the searched scan is cast from
 CENTRE = np.array([0.6, 0.22, 0.13], np.float32)       # 0.02 m / 0.005 rad off it
@@ -62,42 +56,8 @@ def scans(pkg):
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    cxx = clangxx()
-    if cxx is None:
-        pytest.fail("clang++ is needed to compile the kernel text for the CPU")
-    d = tmp_path_factory.mktemp("search_cov_emu")
-    stages = open(os.path.join(CSRC, "pfslam_stages.hip.inc")).read()
-    reg = open(os.path.join(CSRC, "pfslam_register.hip.inc")).read()
-    srch = open(os.path.join(CSRC, "pfslam_search.hip.inc")).read()
-    scan = open(os.path.join(CSRC, "pfslam_search_scan.hip.inc")).read()
-    cov = open(os.path.join(CSRC, "pfslam_search_cov.hip.inc")).read()
-    main = open(os.path.join(CSRC, "pfslam_hip.hip")).read()
-    cuts = [(stages, "template <typename F>\n__device__ __forceinline__ float wave_sum_canonical", "// float <-> order-preserving signed int"),
-            (stages, "namespace pf {\nstruct Sym3", "// ------------------------------------------------------------------------------------------\n// A7/A8"),
-            (stages, "#define PF_EST_WAVES", "__global__ __launch_bounds__(PF_EST_WAVES * 64) void k_estimate_moments"),
-            (reg, "// REGISTER-KERNEL-TEXT-BEGIN", "// REGISTER-KERNEL-TEXT-END"),
-            (srch, "// SEARCH-KERNEL-TEXT-BEGIN", "// SEARCH-KERNEL-TEXT-END"),
-            (scan, "// SEARCH-SCAN-KERNEL-TEXT-BEGIN", "// SEARCH-SCAN-KERNEL-TEXT-END"),
-            (cov, "// SEARCH-COV-KERNEL-TEXT-BEGIN", "// SEARCH-COV-KERNEL-TEXT-END")]
-    text = ""
-    for src, first, last in cuts:
-        assert src.count(first) == 1 and src.count(last) == 1, "the kernel text has moved: %r" % first
-        text += src[src.index(first):src.index(last, src.index(first))]
-    for name in ("search_derive", "k_search_ends", "k_search_score", "k_search_result", "k_scan_points", "k_scan_fill", "k_scan_splat", "est_moments", "est_centred",
-                 "est_finish", "k_cov_moments", "k_cov_centred", "k_cov_final", "k_cov_small"):
-        assert name in text
-    (d / "search_cov_kernel_text.inc").write_text(text)
-    defs = [re.search(r"^#define %s .*$" % name, main, re.M).group(0) for name in ("PF_LIDAR_RANGE", "PF_SVD_EPSILON", "PF_SUM_TILE")]
-    (d / "register_defines.inc").write_text("\n".join(defs) + "\n")
-    os.makedirs(str(d / "hip"))
-    (d / "hip" / "hip_runtime.h").write_text("// (the shim of search_cov_emu.cpp stands in for the HIP runtime's declarations)\n")
-    for name in ("pf_math.h", "kd_device.h"):
-        shutil.copy(os.path.join(CSRC, name), str(d / name))
-    shutil.copy(os.path.join(ROOT, "tests", "search_cov_emu.cpp"), str(d / "search_cov_emu.cpp"))
-    exe = str(d / "search_cov_emu")
-    subprocess.check_call([cxx, "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-Wno-unknown-attributes", "-pthread", "-I", str(d), str(d / "search_cov_emu.cpp"), "-o", exe])
-    return d, exe
+    return KT.build(tmp_path_factory, "search_cov", ("search_derive", "k_search_ends", "k_search_score", "k_search_result", "k_scan_points", "k_scan_fill", "k_scan_splat", "est_moments",
+                                                    "est_centred", "est_finish", "k_cov_moments", "k_cov_centred", "k_cov_final", "k_cov_small"), ("PF_LIDAR_RANGE", "PF_SVD_EPSILON", "PF_SUM_TILE"))
 
 
 def run_emu(emu, tag, ref_scan, ref_pose, scan, centre, opts, sigma, res=0.025):
@@ -112,8 +72,7 @@ def run_emu(emu, tag, ref_scan, ref_pose, scan, centre, opts, sigma, res=0.025):
                          np.float32).tobytes())
         f.write(ref_scan.tobytes())
         f.write(scan.tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    KT.run(exe, fin, fout)
     raw = np.fromfile(fout, np.int32)
     out = raw[:12].view(np.float32).copy()
     assert out[3] == 0 and out[11] == 0

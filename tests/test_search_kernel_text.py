@@ -6,20 +6,15 @@ requests) as a stand-alone program with -ffp-contract=off like the library, unde
 and the full score volume must be the restatement's (tests/search_ref.py), bit for bit and integer for integer -- which also shows
 that no index leaves the field, the end-point list or the volume.  What it cannot show is the GPU's arithmetic and memory model:
 tests/test_gpu_search.py does."""
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import kernel_text as KT
+from kernel_text import device_arrays
 import register_ref as R
 import search_ref as S
-from test_register_kernel_text import clangxx, device_arrays
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gpu-icp-slam_amd", "csrc")
 CENTRE = np.array([0.6, 0.22, 0.13], np.float32)     # 0.10 m / 0.03 rad off the pose the scan was cast from
 # (map, beams, options): windows 1x1x1, 3x1x1 and 5x5x3, a 70-wide row (a partial second wave), stride 1 and 3
 CASES = [("p4000", 1, dict(half_x=0, half_y=0, half_theta=0)),
@@ -42,36 +37,7 @@ def maps(pkg):
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    cxx = clangxx()
-    if cxx is None:
-        pytest.fail("clang++ is needed to compile the kernel text for the CPU")
-    d = tmp_path_factory.mktemp("search_emu")
-    stages = open(os.path.join(CSRC, "pfslam_stages.hip.inc")).read()
-    reg = open(os.path.join(CSRC, "pfslam_register.hip.inc")).read()
-    srch = open(os.path.join(CSRC, "pfslam_search.hip.inc")).read()
-    main = open(os.path.join(CSRC, "pfslam_hip.hip")).read()
-    cuts = [(stages, "template <typename F>\n__device__ __forceinline__ float wave_sum_canonical", "// float <-> order-preserving signed int"),
-            (stages, "namespace pf {\nstruct Sym3", "// ------------------------------------------------------------------------------------------\n// A7/A8"),
-            (reg, "// REGISTER-KERNEL-TEXT-BEGIN", "// REGISTER-KERNEL-TEXT-END"),
-            (srch, "// SEARCH-KERNEL-TEXT-BEGIN", "// SEARCH-KERNEL-TEXT-END")]
-    text = ""
-    for src, first, last in cuts:
-        assert src.count(first) == 1 and src.count(last) == 1, "the kernel text has moved: %r" % first
-        text += src[src.index(first):src.index(last, src.index(first))]
-    for name in ("search_derive", "k_search_ends", "k_search_field", "k_search_score", "k_search_result", "kd_nearest_exact"):
-        assert name in text
-    (d / "search_kernel_text.inc").write_text(text)
-    defs = [re.search(r"^#define %s .*$" % name, main, re.M).group(0) for name in ("PF_LIDAR_RANGE", "PF_SVD_EPSILON")]
-    (d / "register_defines.inc").write_text("\n".join(defs) + "\n")
-    os.makedirs(str(d / "hip"))
-    (d / "hip" / "hip_runtime.h").write_text("// (the shim of search_emu.cpp stands in for the HIP runtime's declarations)\n")
-    for name in ("pf_math.h", "kd_device.h"):
-        shutil.copy(os.path.join(CSRC, name), str(d / name))
-    shutil.copy(os.path.join(ROOT, "tests", "search_emu.cpp"), str(d / "search_emu.cpp"))
-    exe = str(d / "search_emu")
-    subprocess.check_call([cxx, "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-Wno-unknown-attributes", "-pthread", "-I", str(d), str(d / "search_emu.cpp"), "-o", exe])
-    return d, exe
+    return KT.build(tmp_path_factory, "search", ("search_derive", "k_search_ends", "k_search_field", "k_search_score", "k_search_result", "kd_nearest_exact"), ("PF_LIDAR_RANGE", "PF_SVD_EPSILON"))
 
 
 def run_emu(emu, tag, tree, scan, centre, opts, res=0.025):
@@ -86,8 +52,7 @@ def run_emu(emu, tag, tree, scan, centre, opts, res=0.025):
         f.write(np.array([centre[0], centre[1], centre[2], o["step_theta"], o["max_dist"], res, 0, 0], np.float32).tobytes())
         for a in (hot, z, parent, w, scan):
             f.write(np.ascontiguousarray(a).tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    KT.run(exe, fin, fout)
     raw = np.fromfile(fout, np.int32)
     out = raw[:12].view(np.float32)
     assert out[3] == 0 and out[11] == 0

@@ -1,25 +1,20 @@
 """The pfslam_search_wide kernels' own text, run on the CPU (no GPU needed): tests/search_wide_emu.cpp compiles the four kernels cut out of
 csrc/pfslam_search_wide.hip.inc -- behind the text of csrc/pfslam_search.hip.inc (k_search_ends, k_search_field, k_search_result, launched
-as they are) and what that text reuses, none of it changed -- behind the SIMT shim of tests/search_emu.cpp as a stand-alone program with
+as they are) and what that text reuses, none of it changed -- behind the SIMT shim (tests/simt_shim.h) as a stand-alone program with
 -ffp-contract=off like the library, under AddressSanitizer and UBSan, every buffer at exactly the size pfslam_search_wide requests.  The
 winner and the info must be the restatement's (tests/search_ref.py: the full volume's smallest score, the lowest k among equal ones), bit
 for bit -- which also shows that no index leaves a field level, the end-point list or a frontier buffer, whatever the frontier's size.
 What it cannot show is the GPU's arithmetic and memory model: tests/test_gpu_search_wide.py does."""
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import kernel_text as KT
+from kernel_text import device_arrays
 import register_ref as R
 import search_ref as S
 import search_wide_ref as Wd
-from test_register_kernel_text import clangxx, device_arrays
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gpu-icp-slam_amd", "csrc")
 CENTRE = np.array([0.6, 0.22, 0.13], np.float32)     # 0.10 m / 0.03 rad off the pose the scan was cast from
 ROOM = 1 << 22                                       # the library's frontier
 # (map, beams, options, frontier nodes): 1x1x1 (top level 0), 5x3x1 (smaller than one top block), 71x9x3 at stride 3 (two top blocks a
@@ -42,38 +37,8 @@ def maps(pkg):
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    cxx = clangxx()
-    if cxx is None:
-        pytest.fail("clang++ is needed to compile the kernel text for the CPU")
-    d = tmp_path_factory.mktemp("search_wide_emu")
-    stages = open(os.path.join(CSRC, "pfslam_stages.hip.inc")).read()
-    reg = open(os.path.join(CSRC, "pfslam_register.hip.inc")).read()
-    srch = open(os.path.join(CSRC, "pfslam_search.hip.inc")).read()
-    wide = open(os.path.join(CSRC, "pfslam_search_wide.hip.inc")).read()
-    main = open(os.path.join(CSRC, "pfslam_hip.hip")).read()
-    cuts = [(stages, "template <typename F>\n__device__ __forceinline__ float wave_sum_canonical", "// float <-> order-preserving signed int"),
-            (stages, "namespace pf {\nstruct Sym3", "// ------------------------------------------------------------------------------------------\n// A7/A8"),
-            (reg, "// REGISTER-KERNEL-TEXT-BEGIN", "// REGISTER-KERNEL-TEXT-END"),
-            (srch, "// SEARCH-KERNEL-TEXT-BEGIN", "// SEARCH-KERNEL-TEXT-END"),
-            (wide, "// SEARCH-WIDE-KERNEL-TEXT-BEGIN", "// SEARCH-WIDE-KERNEL-TEXT-END")]
-    text = ""
-    for src, first, last in cuts:
-        assert src.count(first) == 1 and src.count(last) == 1, "the kernel text has moved: %r" % first
-        text += src[src.index(first):src.index(last, src.index(first))]
-    for name in ("search_derive", "k_search_ends", "k_search_field", "k_search_result", "k_wide_pyramid", "k_wide_top", "k_wide_score", "k_wide_expand", "kd_nearest_exact"):
-        assert name in text
-    (d / "search_wide_kernel_text.inc").write_text(text)
-    defs = [re.search(r"^#define %s .*$" % name, main, re.M).group(0) for name in ("PF_LIDAR_RANGE", "PF_SVD_EPSILON")]
-    (d / "register_defines.inc").write_text("\n".join(defs) + "\n")
-    os.makedirs(str(d / "hip"))
-    (d / "hip" / "hip_runtime.h").write_text("// (the shim of search_wide_emu.cpp stands in for the HIP runtime's declarations)\n")
-    for name in ("pf_math.h", "kd_device.h"):
-        shutil.copy(os.path.join(CSRC, name), str(d / name))
-    shutil.copy(os.path.join(ROOT, "tests", "search_wide_emu.cpp"), str(d / "search_wide_emu.cpp"))
-    exe = str(d / "search_wide_emu")
-    subprocess.check_call([cxx, "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-Wno-unknown-attributes", "-pthread", "-I", str(d), str(d / "search_wide_emu.cpp"), "-o", exe])
-    return d, exe
+    return KT.build(tmp_path_factory, "search_wide", ("search_derive", "k_search_ends", "k_search_field", "k_search_result", "k_wide_pyramid", "k_wide_top", "k_wide_score",
+                                                     "k_wide_expand", "kd_nearest_exact"), ("PF_LIDAR_RANGE", "PF_SVD_EPSILON"))
 
 
 def run_emu(emu, tag, tree, scan, centre, opts, room=ROOM, res=0.025):
@@ -88,8 +53,7 @@ def run_emu(emu, tag, tree, scan, centre, opts, room=ROOM, res=0.025):
         f.write(np.array([centre[0], centre[1], centre[2], o["step_theta"], o["max_dist"], res, 0, 0], np.float32).tobytes())
         for a in (hot, z, parent, w, scan):
             f.write(np.ascontiguousarray(a).tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    KT.run(exe, fin, fout)
     raw = np.fromfile(fout, np.uint8)
     out = raw[:48].view(np.float32)
     stats = raw[48:112].view(np.int64)
