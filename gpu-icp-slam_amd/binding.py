@@ -29,6 +29,7 @@ SYMBOLS = [
     "pfslam_nearest", "pfslam_register", "pfslam_register_default_opts", "pfslam_register_batch", "pfslam_search", "pfslam_search_default_opts", "pfslam_search_scan", "pfslam_search_wide",
     "pfslam_search_cov", "pfslam_search_scan_cov", "pfslam_search_cov_default_opts", "pfslam_search_best", "pfslam_search_best_default_opts",
     "pfslam_cast", "pfslam_cast_default_opts", "pfslam_map_raster", "pfslam_cast_score", "pfslam_cast_score_default_opts",
+    "pfslam_move_particles", "pfslam_move_default_opts",
     "pfslam_time_score_grid", "pfslam_set_shard_balance", "pfslam_shard_balance_due", "pfslam_shard_balance_build", "pfslam_shard_balance_adopt",
 ]
 
@@ -75,6 +76,12 @@ class CastScoreOpts(C.Structure):
     """pfslam_cast_score_opts (include/pfslam.h)."""
     _fields_ = [("tol", C.c_float), ("clip", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float), ("count_miss", C.c_int32), ("source", C.c_int32),
                 ("reserved_", C.c_int32 * 2)]
+
+
+class MoveOpts(C.Structure):
+    """pfslam_move_opts (include/pfslam.h)."""
+    _fields_ = [("ref_theta", C.c_float), ("cov_scale", C.c_float), ("sigma_xy_min", C.c_float), ("sigma_theta_min", C.c_float),
+                ("reserved_", C.c_int32 * 4)]
 
 
 CAST_SCORE_COLUMNS = ("valid", "agree", "through", "short", "miss", "q1", "q2", "cost")
@@ -206,6 +213,9 @@ def load():
     L.pfslam_cast_score_default_opts.restype = None
     L.pfslam_cast_score_default_opts.argtypes = [vp]
     L.pfslam_cast_score.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.pfslam_move_default_opts.restype = None
+    L.pfslam_move_default_opts.argtypes = [vp]
+    L.pfslam_move_particles.argtypes = [vp, i32, vp, vp, vp]
     L.pfslam_debug_check_cells.argtypes = [vp, vp]
     L.pfslam_set_probe.argtypes = [vp, i32]
     L.pfslam_get_probe.argtypes = [vp, vp, i32, vp, vp]
@@ -433,6 +443,27 @@ class PfSlam:
         """Odometry hook: every particle and robotPos += (dx, dy, dtheta)."""
         d = np.ascontiguousarray(delta, dtype=np.float32)
         _chk(self.L.pfslam_shift_particles(self._h, _p(d)), "pfslam_shift_particles")
+
+    def move_particles(self, frame, delta, cov=None, ref_theta=0.0, cov_scale=1.0, sigma_xy_min=0.0, sigma_theta_min=0.0):
+        """The odometry motion model (include/pfslam.h, pfslam_move_particles): every particle moves by `delta` = (dx, dy, dtheta), given
+        in the frame of heading `ref_theta`, rotated into its own frame, plus Gaussian noise of covariance cov_scale * cov + the floors,
+        drawn per (frame, global particle index).  cov: None (zero), the six entries xx, xy, xtheta, yy, ytheta, thetatheta (raw[3:9] of
+        search_cov() / search_scan_cov()) or their symmetric 3 x 3 matrix (the dict's "cov").  Enqueued behind the frames in flight."""
+        d = np.ascontiguousarray(delta, dtype=np.float32).reshape(-1)
+        if d.shape != (3,):
+            raise ValueError("move_particles(): delta must be (dx, dy, dtheta), got %d values" % d.size)
+        c = None
+        if cov is not None:
+            c = np.ascontiguousarray(cov, dtype=np.float32)
+            if c.shape == (3, 3):
+                c = np.ascontiguousarray(c[[0, 0, 0, 1, 1, 2], [0, 1, 2, 1, 2, 2]])
+            c = c.reshape(-1)
+            if c.shape != (6,):
+                raise ValueError("move_particles(): cov must hold 6 entries or be 3 x 3, got %d values" % c.size)
+        o = MoveOpts()
+        self.L.pfslam_move_default_opts(C.byref(o))
+        o.ref_theta, o.cov_scale, o.sigma_xy_min, o.sigma_theta_min = ref_theta, cov_scale, sigma_xy_min, sigma_theta_min
+        _chk(self.L.pfslam_move_particles(self._h, frame, _p(d), None if c is None else _p(c), C.byref(o)), "pfslam_move_particles")
 
     def motion_update(self, frame):
         _chk(self.L.pfslam_motion_update(self._h, frame), "pfslam_motion_update")

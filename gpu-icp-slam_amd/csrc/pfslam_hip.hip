@@ -1588,11 +1588,11 @@ __global__ __launch_bounds__(256) void k_shift(float *__restrict__ x, float *__r
     y[i] = y[i] + dy;
     th[i] = th[i] + dt;
 }
-// Every pose the filter holds -- all particles and robotPos -- moves by the same increment (one float addition per component).
-// Enqueued behind the frames in flight; no host wait.
-extern "C" int pfslam_shift_particles(pfslam_handle *h, const float delta[3])
+// What the odometry calls (pfslam_shift_particles, pfslam_move_particles: csrc/pfslam_move.hip.inc) share around their one launch on the
+// particle stream: enqueued behind the frames in flight, no host wait, nothing booked.  `ad` bounds how far any heading moves.
+template <typename Launch>
+static int enqueue_odometry(pfslam_handle *h, float ad, Launch launch)
 {
-    if (!h || !delta) return fail("pfslam_shift_particles: bad argument");
     HIPCHK(hipSetDevice(h->cfg.device));
     CHK(join_map(h)); // the map update a frame left on the aux stream reads the pose
     if (h->pipe_live && !h->serial) { // round-5 frames: the pose's readers of the last frame are k_walls (chain) and the free-cell chain
@@ -1604,18 +1604,27 @@ extern "C" int pfslam_shift_particles(pfslam_handle *h, const float delta[3])
         }
         HIPCHK(hipStreamWaitEvent(h->stream, h->ev_ftail, 0));
     }
-    const float ad = delta[2] == delta[2] ? fabsf(delta[2]) : INFINITY;
     h->theta_shift += ad; // (headers of frames enqueued before this do not know of it)
     h->theta_bound += ad; // ... and the choice of the scan-match kernel's instantiation must: the bound itself moves at once
     h->theta_shift_seq = h->seq;
-    hipLaunchKernelGGL(k_shift, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, h->x, h->y, h->th, h->n, delta[0], delta[1], delta[2], h->pose,
-                       h->cloud_valid ? h->cloud : (float *)nullptr);
+    launch();
     HIPCHK(hipGetLastError());
     if (h->pipe_live) {
         HIPCHK(hipEventRecord(h->ev_shift, h->stream));
         h->shift_pending = true;
     }
     return 0;
+}
+// Every pose the filter holds -- all particles and robotPos -- moves by the same increment (one float addition per component).
+// Enqueued behind the frames in flight; no host wait.
+extern "C" int pfslam_shift_particles(pfslam_handle *h, const float delta[3])
+{
+    if (!h || !delta) return fail("pfslam_shift_particles: bad argument");
+    const float ad = delta[2] == delta[2] ? fabsf(delta[2]) : INFINITY;
+    return enqueue_odometry(h, ad, [&] {
+        hipLaunchKernelGGL(k_shift, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, h->x, h->y, h->th, h->n, delta[0], delta[1], delta[2], h->pose,
+                           h->cloud_valid ? h->cloud : (float *)nullptr);
+    });
 }
 
 // ---- A5 -------------------------------------------------------------------------------------
@@ -2511,3 +2520,4 @@ static int frame_v2_finish(pfslam_handle *h);
 #include "pfslam_search_best.hip.inc"
 #include "pfslam_cast.hip.inc"
 #include "pfslam_cast_score.hip.inc"
+#include "pfslam_move.hip.inc"

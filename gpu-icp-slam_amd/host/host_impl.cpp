@@ -408,6 +408,22 @@ void pfslamShiftParticles(glm::vec3 delta)
     const float d[3] = {delta.x, delta.y, delta.z};
     PFCHK(pfslam_shift_particles(g_handle, d), "pfslamShiftParticles");
 }
+bool pfslamMoveParticles(int frame, glm::vec3 delta, const float cov[6], float ref_theta, float sigma_xy_min, float sigma_theta_min, float cov_scale)
+{
+    if (!g_handle) return false;
+    pfslam_move_opts o;
+    pfslam_move_default_opts(&o);
+    o.ref_theta = ref_theta;
+    o.cov_scale = cov_scale;
+    o.sigma_xy_min = sigma_xy_min;
+    o.sigma_theta_min = sigma_theta_min;
+    const float d[3] = {delta.x, delta.y, delta.z};
+    if (pfslam_move_particles(g_handle, frame, d, cov, &o)) {
+        fprintf(stderr, "pfslamMoveParticles: %s\n", pfslam_last_error());
+        return false;
+    }
+    return true;
+}
 bool pfslamSearchWide(glm::vec3 centre, float half_metres, float half_radians, glm::vec3 &pose, long long *index)
 {
     if (!g_handle) return false;

@@ -95,6 +95,14 @@ bool pfslamSearchCov(glm::vec3 centre, float sigma, glm::vec3 &pose, float cov[1
 bool pfslamSearchScanCov(const float *ref_scan, glm::vec3 ref_pose, float sigma, glm::vec3 &pose, float cov[16], int *index, const float *scan = nullptr);
 // The odometry hook (include/pfslam.h, pfslam_shift_particles): every particle and the robot's pose += delta.
 void pfslamShiftParticles(glm::vec3 delta);
+// The odometry motion model (include/pfslam.h, pfslam_move_particles): every particle moves by `delta`, given in the frame of heading
+// `ref_theta`, rotated into its own frame, plus Gaussian noise of covariance cov_scale * cov + the floors sigma_xy_min^2 (x, y) and
+// sigma_theta_min^2 (heading), drawn per (frame, particle); the robot's pose moves without noise.  cov: the six entries xx, xy, xtheta, yy,
+// ytheta, thetatheta -- cov + 3 of pfslamSearchCov / pfslamSearchScanCov, with delta = pose - ref_pose and ref_theta = ref_pose.z of that
+// search --, or null for none.  Enqueued behind the frames in flight.  false (and a line on stderr): no live filter, a value that is not
+// finite, a negative scale or floor, or a covariance that is not positive semi-definite; nothing has moved then.
+bool pfslamMoveParticles(int frame, glm::vec3 delta, const float cov[6], float ref_theta, float sigma_xy_min = 0.0f, float sigma_theta_min = 0.0f,
+                         float cov_scale = 1.0f);
 // The same winner over a window too large to score candidate by candidate (include/pfslam.h, pfslam_search_wide): +-half_metres in x and
 // y at stride 1 (rounded to map cells) and +-half_radians in steps of 0.0125 rad (rounded down) around `centre`, the default max_dist;
 // found by branch and bound, exactly.  *index is the exact candidate number (it can pass 2^24, where a float rounds), -1 as above; it

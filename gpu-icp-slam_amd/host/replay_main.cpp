@@ -1,5 +1,5 @@
 // replay_main.cpp -- headless counterpart of the reference's main loop (main.cpp:47-96, 175-229):
-//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [cast=1] [castscore=1] [export=PREFIX]
+//   pfslam_replay <scene.txt> <lidar.f32|.mat> [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1|2] [cast=1] [castscore=1] [export=PREFIX]
 //     grid           the 2-D occupancy-grid stages instead of the point-cloud ones
 //     loop           UpdateTopology + CheckLoopClosure at the end of every frame (kernel.cu:1750-1751, commented out in
 //                    the reference's shipped step); loop-closure proposals are printed per frame
@@ -21,6 +21,11 @@
 //                    the previous frame's pose (the default window around it); a line "odometry <frame> index <k> delta <dx dy dtheta> bits
 //                    <3 hex words of the winning pose>" and pfslamShiftParticles with that delta before the step ("odometry <frame> none"
 //                    and no shift when the call fails or no heading has an in-range beam)
+//     odometry=2     instead the motion model: pfslamSearchScanCov of the same two scans (the library's default sigma) and
+//                    pfslamMoveParticles(frame, delta, cov + 3, the previous pose's heading) with the floors res / sqrt(12) and
+//                    step_theta / sqrt(12) of the search's lattice; a line "odometry <frame> index <k> delta <dx dy dtheta> sd <the square
+//                    roots of the covariance's three diagonal entries> bits <3 hex words of the winning pose>" ("odometry <frame> none" and
+//                    no move when a call fails or no heading has an in-range beam)
 //     cast=1         a further line per frame: "cast <frame> hits <n> agree <k>": pfslamCastScan from the frame's pose through the frame's map,
 //                    the beams that hit, and the beams whose cast range is within 0.1 m of the scan's ("cast <frame> none" when the call fails or
 //                    the scan does not have the filter's 1081 beams)
@@ -42,7 +47,7 @@
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1] [cast=1] [castscore=1] [export=PREFIX]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt LIDARFILE.f32|.mat [frames] [grid] [loop] [resampler=N] [estimate=1] [register=K] [multistart=K] [search=1|2|3] [odometry=1|2] [cast=1] [castscore=1] [export=PREFIX]\n", argv[0]);
         return 1;
     }
     Scene *scene = new Scene(argv[1]);
@@ -50,7 +55,8 @@ int main(int argc, char **argv)
     size_t last = lidar->scans.size() - 1;
     bool loop = false, estimate = false;
     int register_iters = 0, multistart_iters = 0, search = 0;
-    bool odometry = false, cast = false, castscore = false;
+    int odometry = 0;
+    bool cast = false, castscore = false;
     std::string export_prefix;
     for (int i = 3; i < argc; i++) {
         if (strcmp(argv[i], "grid") == 0) pfslamUseGridMap(true);
@@ -60,7 +66,7 @@ int main(int argc, char **argv)
         else if (strncmp(argv[i], "register=", 9) == 0) register_iters = atoi(argv[i] + 9);
         else if (strncmp(argv[i], "multistart=", 11) == 0) multistart_iters = atoi(argv[i] + 11);
         else if (strncmp(argv[i], "search=", 7) == 0) search = atoi(argv[i] + 7);
-        else if (strncmp(argv[i], "odometry=", 9) == 0) odometry = atoi(argv[i] + 9) != 0;
+        else if (strncmp(argv[i], "odometry=", 9) == 0) odometry = atoi(argv[i] + 9);
         else if (strncmp(argv[i], "cast=", 5) == 0) cast = atoi(argv[i] + 5) != 0;
         else if (strncmp(argv[i], "castscore=", 10) == 0) castscore = atoi(argv[i] + 10) != 0;
         else if (strncmp(argv[i], "export=", 7) == 0) export_prefix = argv[i] + 7;
@@ -74,7 +80,26 @@ int main(int argc, char **argv)
     glm::vec3 last_pose(0.0f);
     while (iteration < last) {
         iteration++;
-        if (odometry && iteration > 1) {
+        if (odometry == 2 && iteration > 1) {
+            glm::vec3 r;
+            int index = -1;
+            float cov[16];
+            bool moved = false;
+            if (pfslamSearchScanCov(lidar->scans[iteration - 1].data(), last_pose, 0.2f, r, cov, &index, lidar->scans[iteration].data()) && index >= 0) {
+                const glm::vec3 d(r.x - last_pose.x, r.y - last_pose.y, r.z - last_pose.z);
+                float res = 0.025f; // pfslam_default_config
+                if (!scene->maps.empty()) res = scene->maps[0].resolution.x;
+                const float step_theta = 0.0125f; // pfslam_search_default_opts
+                if (pfslamMoveParticles((int)iteration, d, cov + 3, last_pose.z, res / sqrtf(12.0f), step_theta / sqrtf(12.0f))) {
+                    unsigned int b[3];
+                    memcpy(&b[0], &r.x, 4); memcpy(&b[1], &r.y, 4); memcpy(&b[2], &r.z, 4);
+                    printf("odometry %zu index %d delta %.6f %.6f %.6f sd %.6f %.6f %.6f bits %08x %08x %08x\n", iteration, index, d.x, d.y, d.z,
+                           sqrtf(cov[3]), sqrtf(cov[6]), sqrtf(cov[8]), b[0], b[1], b[2]);
+                    moved = true;
+                }
+            }
+            if (!moved) printf("odometry %zu none\n", iteration);
+        } else if (odometry && iteration > 1) {
             glm::vec3 r;
             int index = -1;
             if (pfslamSearchScan(lidar->scans[iteration - 1].data(), last_pose, r, &index, lidar->scans[iteration].data()) && index >= 0) {

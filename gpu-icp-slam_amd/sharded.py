@@ -144,6 +144,10 @@ class ShardedSlam:
     def shift_particles(self, delta):
         """Odometry increment: every pose of every shard and the (replicated) robot pose move by the same (dx, dy, dtheta)."""
         self.eng.shift_particles(delta)
+    def move_particles(self, frame, delta, cov=None, **opts):
+        """The odometry motion model (PfSlam.move_particles): every rank calls it with the same arguments; the draw is keyed by the global
+        particle index, so the shards together are the unsharded cloud bit for bit."""
+        self.eng.move_particles(frame, delta, cov, **opts)
     def set_particles(self, p_global):
         """The GLOBAL particle array (every rank passes the same one); this rank keeps its shard."""
         self.eng.set_particles(np.ascontiguousarray(p_global[self.goff:self.goff + self.n]))

@@ -672,6 +672,72 @@ int pfslam_search_scan_cov(pfslam_handle *h, const float *ref_scan_host, const f
                            const float *scan_host /* NULL = the handle's scan */, const float centre[3] /* NULL = ref_pose */,
                            const pfslam_search_opts *opts, const pfslam_cov_opts *cov, float pose_out[3], float info[8], float cov_out[16],
                            int32_t *scores /* NULL or one int per candidate */);
+/* pfslam_move_particles: the odometry motion model (no reference counterpart: the reference's filter has no motion model besides the
+ * diffusion of kernel.cu:375-397).  pfslam_shift_particles adds one world-frame increment to every pose, which is wrong as soon as the
+ * cloud's headings differ, and drops the increment's uncertainty.  Here every particle moves by the increment ROTATED INTO ITS OWN FRAME
+ * and gets correlated Gaussian noise drawn from a 3 x 3 covariance laid out as pfslam_search_cov / pfslam_search_scan_cov write it:
+ * cov = cov_out + 3, with delta = pose_out - ref_pose and ref_theta = ref_pose[2] of the same search.  The draw is deterministic, keyed
+ * by `frame` and the GLOBAL particle index, and bit-identical for any sharding.
+ * Specification.  All arithmetic is float, one rounding per operation, in the order written, no contraction; fdiv and fsqrt are
+ * correctly rounded.
+ *   factor L (host, once per call)
+ *             c = cov, or zeros when cov is NULL
+ *             a00 = cov_scale * c[0] + sigma_xy_min * sigma_xy_min
+ *             a10 = cov_scale * c[1]
+ *             a20 = cov_scale * c[2]
+ *             a11 = cov_scale * c[3] + sigma_xy_min * sigma_xy_min
+ *             a21 = cov_scale * c[4]
+ *             a22 = cov_scale * c[5] + sigma_theta_min * sigma_theta_min
+ *             Cholesky, lower:
+ *             p0 = a00;                          L00 = fsqrt(p0), L10 = fdiv(a10, L00), L20 = fdiv(a20, L00)
+ *             p1 = a11 - L10 * L10;              L11 = fsqrt(p1), L21 = fdiv(a21 - L20 * L10, L11)
+ *             p2 = a22 - (L20 * L20 + L21 * L21); L22 = fsqrt(p2)
+ *             A pivot that is exactly 0 makes its whole column of L zero, with no division.  A pivot that is negative or not finite is
+ *             refused ("covariance is not positive semi-definite").
+ *   particle  with LOCAL index i and GLOBAL index g = global_offset + i:
+ *             e = engine_seed(frame, g, 1)        (depth 1: a stream of its own beside the dispersion's engine_seed(frame, g, 0))
+ *             z1, z2, z3 = normal(e, 0, 1), three successive draws (pf::normal of csrc/pf_math.h; pfslam_set_trig picks its device-library
+ *             form, as in the dispersion)
+ *             mx  = delta[0] + L00 * z1
+ *             my  = delta[1] + (L10 * z1 + L11 * z2)
+ *             mt  = delta[2] + ((L20 * z1 + L21 * z2) + L22 * z3)
+ *             phi = theta_i - ref_theta
+ *             (s, c) = sincosf_spec(phi)          (pfslam_set_trig 1: the device library's sinf / cosf)
+ *             x'     = x + ((c * mx) - (s * my))
+ *             y'     = y + ((s * mx) + (c * my))
+ *             theta' = theta + mt
+ *   robot pose  the same formulas with z1 = z2 = z3 = 0 and phi = pose.theta - ref_theta.
+ *   weights     untouched.
+ * Identity.  With cov == NULL, zero floors and every heading equal to ref_theta (phi = 0: s = 0, c = 1) the particles are those of
+ * pfslam_shift_particles(delta) bit for bit, for operands that are not signed zeros.
+ * Remarks.  A cov from a search whose Neff is near 1 says the posterior is narrower than the search's lattice: it needs the floors, the
+ * quantisation deviations sigma_xy_min = stride res / sqrt(12) and sigma_theta_min = step_theta / sqrt(12) (see pfslam_search_cov's
+ * remarks).  cov_scale tempers or inflates the covariance as a whole (0: the floors alone).  Headings are not wrapped, as everywhere.
+ * The host's bound on |heading| (it selects the scan-match kernel's instantiation) grows at once by
+ * |delta[2]| + 7 (|L20| + |L21| + |L22|): 7 is the next integer above the largest |normal(., 0, 1)| the generator can return (the draw
+ * u = 0, 6.2303).
+ * Refused (non-zero, pfslam_last_error names the cause under this function's name, nothing is enqueued), in this order: a NULL h, delta
+ * or opts; a delta, cov entry, ref_theta, cov_scale or floor that is not finite; a negative cov_scale or floor; a reserved_ that is not
+ * 0; a bad pivot.
+ * Method.  k_move (csrc/pfslam_move.hip.inc): one thread per particle, coalesced SoA, 256-thread workgroups, like the dispersion's
+ * kernel; L, delta, ref_theta, frame, the global offset and the trig mode are kernel arguments; no LDS, no scratch, no atomics; its cost
+ * is three erfcinv evaluations and one sincos in fp64.  One thread moves the robot's pose and, by the pose's increment, the cloud
+ * statistics the next frame's lane order starts from (performance only).  Like pfslam_shift_particles the call does NOT book the frames
+ * in flight: it is enqueued behind them on the particle stream, with the same edges, and there is no host wait.  Sharded handles: every
+ * rank calls it with the same arguments; only g enters the draw, so the concatenated shards equal the unsharded handle bit for bit.
+ * Measured: profiles/move_particles.txt. */
+typedef struct pfslam_move_opts {
+    float   ref_theta;        /* heading (rad) of the frame `delta` and `cov` are expressed in; finite */
+    float   cov_scale;        /* finite, >= 0 */
+    float   sigma_xy_min;     /* m,   finite, >= 0 */
+    float   sigma_theta_min;  /* rad, finite, >= 0 */
+    int32_t reserved_[4];     /* must be 0 */
+} pfslam_move_opts;
+/* {0, 1, 0, 0, {0, 0, 0, 0}} */
+void pfslam_move_default_opts(pfslam_move_opts *o);
+int pfslam_move_particles(pfslam_handle *h, int frame, const float delta[3],
+                          const float cov[6] /* NULL = zero; xx, xy, xtheta, yy, ytheta, thetatheta: cov_out + 3 of pfslam_search*_cov */,
+                          const pfslam_move_opts *opts);
 /* pfslam_search_wide: pfslam_search's winner over windows far beyond its cap (no reference counterpart) -- "where on this map was this scan
  * taken", at any heading: the kidnapped robot, a restart on a saved map, a loop-closure candidate checked at every heading.  +-20 m and a
  * full turn on a 40 m map at 0.025 m are 1601 x 1601 x 503 = 1 289 290 103 candidates: 77 pfslam_search calls at the cap.

@@ -1,0 +1,146 @@
+"""pfslam_move_particles restated from the CPU oracle's primitives.
+
+TEST INFRASTRUCTURE (helper module, not a test).  The CPU oracle is frozen and has no motion model; this restates the specification of
+include/pfslam.h with numpy float32 element-wise operations (one rounding each, in the order written; numpy's float32 sqrt and divide are
+correctly rounded) and takes the generator and the trigonometry from the oracle: orc_engine_seed, orc_normal, orc_sincosf.
+
+    a   = cov_scale * cov + floors,  L = its lower Cholesky factor (a zero pivot: a zero column)
+    e   = engine_seed(frame, g, 1);  z1, z2, z3 = normal(e, 0, 1)
+    m   = delta + L z                (mx, my, mt; the sums in the header's order)
+    phi = theta - ref_theta;  x' = x + (c mx - s my),  y' = y + (s mx + c my),  theta' = theta + mt
+
+tests/test_move_spec.py holds it against the header's claims; tests/test_move_kernel_text.py and tests/test_gpu_move.py hold the kernel to
+it bit for bit."""
+import ctypes as C
+
+import numpy as np
+
+import oracle_lib as O
+
+F = np.float32
+MINSTD_M = 2147483647
+# the state whose next minstd output is 1, i.e. u = 0: the generator's most extreme normal draw
+STATE_U0 = pow(48271, -1, MINSTD_M)
+# a full covariance of corridor shape (include/pfslam.h: 0.106 m along, 0.003 m across, 0.00037 rad), every pair correlated
+SD = (0.106, 0.003, 0.00037)
+CORRIDOR_COV = np.array([SD[0] * SD[0], 0.3 * SD[0] * SD[1], -0.2 * SD[0] * SD[2], SD[1] * SD[1], 0.4 * SD[1] * SD[2], SD[2] * SD[2]], F)
+STAT_N, STAT_FRAME, STAT_DELTA = 65536, 7, np.array([0.5, -0.03, 0.02], F)
+
+
+class NotPsd(ValueError):
+    pass
+
+
+def factor(cov=None, cov_scale=1.0, sigma_xy_min=0.0, sigma_theta_min=0.0):
+    """(L, a): L = (L00, L10, L11, L20, L21, L22) and a = (a00, a10, a20, a11, a21, a22) as float32; NotPsd for a bad pivot."""
+    c = np.zeros(6, F) if cov is None else np.ascontiguousarray(cov, F).reshape(6)
+    s, fxy, ft = F(cov_scale), F(sigma_xy_min) * F(sigma_xy_min), F(sigma_theta_min) * F(sigma_theta_min)
+    with np.errstate(all="ignore"):
+        a00, a10, a20 = F(s * c[0]) + fxy, F(s * c[1]), F(s * c[2])
+        a11, a21, a22 = F(s * c[3]) + fxy, F(s * c[4]), F(s * c[5]) + ft
+        bad = lambda p: not (p >= 0) or np.isinf(p)
+        l00 = l10 = l20 = l11 = l21 = l22 = F(0)
+        p0 = a00
+        if bad(p0):
+            raise NotPsd("covariance is not positive semi-definite")
+        if p0 != 0:
+            l00 = np.sqrt(p0)
+            l10, l20 = F(a10 / l00), F(a20 / l00)
+        p1 = F(a11 - F(l10 * l10))
+        if bad(p1):
+            raise NotPsd("covariance is not positive semi-definite")
+        if p1 != 0:
+            l11 = np.sqrt(p1)
+            l21 = F(F(a21 - F(l20 * l10)) / l11)
+        p2 = F(a22 - F(F(l20 * l20) + F(l21 * l21)))
+        if bad(p2):
+            raise NotPsd("covariance is not positive semi-definite")
+        if p2 != 0:
+            l22 = np.sqrt(p2)
+    return np.array([l00, l10, l11, l20, l21, l22], F), np.array([a00, a10, a20, a11, a21, a22], F)
+
+
+def draws(frame, g):
+    """z[len(g), 3]: the three successive normal(e, 0, 1) of engine_seed(frame, g, 1) for every global index in g."""
+    L = O.lib()
+    z = np.empty((len(g), 3), F)
+    st = C.c_uint32()
+    for r, gi in enumerate(g):
+        st.value = L.orc_engine_seed(int(frame), int(gi), 1)
+        z[r, 0] = L.orc_normal(C.byref(st), 0.0, 1.0)
+        z[r, 1] = L.orc_normal(C.byref(st), 0.0, 1.0)
+        z[r, 2] = L.orc_normal(C.byref(st), 0.0, 1.0)
+    return z
+
+
+def z_max():
+    """|normal(., 0, 1)| of the u = 0 draw: the largest the generator can return."""
+    st = C.c_uint32(STATE_U0)
+    return abs(float(O.lib().orc_normal(C.byref(st), 0.0, 1.0)))
+
+
+def increments(z, delta, L):
+    """(mx, my, mt) of every row of z."""
+    d = np.ascontiguousarray(delta, F)
+    z1, z2, z3 = z[:, 0], z[:, 1], z[:, 2]
+    mx = d[0] + L[0] * z1
+    my = d[1] + (L[1] * z1 + L[2] * z2)
+    mt = d[2] + ((L[3] * z1 + L[4] * z2) + L[5] * z3)
+    return mx, my, mt
+
+
+def apply(x, y, th, mx, my, mt, ref_theta):
+    x, y, th = (np.ascontiguousarray(v, F) for v in (x, y, th))
+    s, c = O.sincosf(th - F(ref_theta))
+    return x + ((c * mx) - (s * my)), y + ((s * mx) + (c * my)), th + mt
+
+
+def move(x, y, th, frame, delta, cov=None, ref_theta=0.0, cov_scale=1.0, sigma_xy_min=0.0, sigma_theta_min=0.0, goff=0):
+    """The particles after pfslam_move_particles: (x', y', theta') as float32 arrays."""
+    L, _ = factor(cov, cov_scale, sigma_xy_min, sigma_theta_min)
+    z = draws(frame, goff + np.arange(len(x)))
+    return apply(x, y, th, *increments(z, delta, L), ref_theta)
+
+
+def move_pose(pose, delta, cov=None, ref_theta=0.0, cov_scale=1.0, sigma_xy_min=0.0, sigma_theta_min=0.0):
+    """The robot's pose after the call: the same formulas with z = 0."""
+    L, _ = factor(cov, cov_scale, sigma_xy_min, sigma_theta_min)
+    p = np.ascontiguousarray(pose, F).reshape(1, 3)
+    x, y, t = apply(p[:, 0], p[:, 1], p[:, 2], *increments(np.zeros((1, 3), F), delta, L), ref_theta)
+    return np.array([x[0], y[0], t[0]], F)
+
+
+def theta_growth(delta, L, z=7.0):
+    """What the host's heading bound grows by."""
+    return F(abs(F(delta[2]))) + F(z) * F(F(abs(L[3]) + abs(L[4])) + abs(L[5]))
+
+
+def cloud(n, ref_theta=0.0, spread=0.2, seed=0, lo=8.0, hi=16.0):
+    """n poses with positions in [lo, hi) and headings ref_theta +- spread, and weights in (0, 1)."""
+    rng = np.random.RandomState(7919 * seed + n)
+    x = rng.uniform(lo, hi, n).astype(F)
+    y = rng.uniform(lo, hi, n).astype(F)
+    th = (ref_theta + rng.uniform(-spread, spread, n)).astype(F)
+    w = rng.uniform(0.1, 1.0, n).astype(F)
+    return x, y, th, w
+
+
+def particles_of(x, y, th, w):
+    p = np.zeros(len(x), O.PARTICLE_DTYPE)
+    p["x"], p["y"], p["theta"], p["w"] = x, y, th, w
+    return p
+
+
+_STAT = {}
+
+
+def stat_case():
+    """The statistics case, computed once and left unchanged: STAT_N particles at the origin with heading 0 = ref_theta, so that the moved
+    particles ARE (mx, my, mt).  Returns (L, a, mx, my, mt)."""
+    if not _STAT:
+        L, a = factor(CORRIDOR_COV)
+        mx, my, mt = increments(draws(STAT_FRAME, np.arange(STAT_N)), STAT_DELTA, L)
+        for v in (L, a, mx, my, mt):
+            v.setflags(write=False)
+        _STAT["v"] = (L, a, mx, my, mt)
+    return _STAT["v"]
