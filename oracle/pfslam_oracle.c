@@ -1618,6 +1618,16 @@ void orc_slam_shift_particles(orc_slam *s, const float d[3])
     }
     for (int k = 0; k < 3; k++) s->robot[k] = s->robot[k] + d[k];
 }
+/* the same hook for a motion model computed outside the oracle (tests/move_ref.py): x, y and theta of all particles, both copies, and
+ * robotPos are replaced; what the shift leaves alone -- every weight, the host copy's mirror weights included -- stays */
+void orc_slam_replace_poses(orc_slam *s, const float *x, const float *y, const float *theta, const float robot[3])
+{
+    for (int i = 0; i < s->cfg.n_particles; i++) {
+        s->dev[i].x = x[i]; s->dev[i].y = y[i]; s->dev[i].theta = theta[i];
+        s->host[i].x = x[i]; s->host[i].y = y[i]; s->host[i].theta = theta[i];
+    }
+    for (int k = 0; k < 3; k++) s->robot[k] = robot[k];
+}
 void orc_slam_get_pose(const orc_slam *s, float pose[3]) { memcpy(pose, s->robot, 12); }
 int orc_slam_kd_size(const orc_slam *s) { return s->kd_size; }
 const orc_node *orc_slam_tree(const orc_slam *s) { return s->kd; }

@@ -192,6 +192,8 @@ void orc_slam_set_grid(orc_slam *s, const int8_t *grid);
 const int8_t *orc_slam_grid(orc_slam *s);
 void orc_slam_set_particles(orc_slam *s, const orc_particle *p); /* device array and host mirror */
 void orc_slam_shift_particles(orc_slam *s, const float d[3]);       /* odometry hook: particles and robotPos += d */
+/* the same hook for a motion model computed by the caller: x, y, theta of both copies and robotPos replaced, no weight touched */
+void orc_slam_replace_poses(orc_slam *s, const float *x, const float *y, const float *theta, const float robot[3]);
 void orc_slam_get_pose(const orc_slam *s, float pose[3]);
 int orc_slam_kd_size(const orc_slam *s);
 const orc_node *orc_slam_tree(const orc_slam *s);

@@ -110,6 +110,14 @@ def move_pose(pose, delta, cov=None, ref_theta=0.0, cov_scale=1.0, sigma_xy_min=
     return np.array([x[0], y[0], t[0]], F)
 
 
+def move_oracle(o, frame, delta, cov=None, **opts):
+    """pfslam_move_particles on a whole-step oracle (oracle_lib.Slam): its particles and pose go through move / move_pose and back through
+    the oracle's pose hook, which writes both particle copies and robotPos and no weight."""
+    p = o.particles()
+    x, y, th = move(p["x"], p["y"], p["theta"], frame, delta, cov, **opts)
+    o.replace_poses(x, y, th, move_pose(o.pose, delta, cov, **opts))
+
+
 def theta_growth(delta, L, z=7.0):
     """What the host's heading bound grows by."""
     return F(abs(F(delta[2]))) + F(z) * F(F(abs(L[3]) + abs(L[4])) + abs(L[5]))
@@ -129,6 +137,62 @@ def particles_of(x, y, th, w):
     p = np.zeros(len(x), O.PARTICLE_DTYPE)
     p["x"], p["y"], p["theta"], p["w"] = x, y, th, w
     return p
+
+
+# ---- the stage's inputs at their edges: one set for the GPU (tests/test_gpu_move.py) and for the kernel text on the CPU
+# (tests/test_move_kernel_text.py), so that a disagreement on the device is split between arithmetic and indexing
+EDGE_N, EDGE_FRAME, EDGE_REF = 257, 9, 0.7
+EDGE_DELTA = np.array([0.31, -0.07, 0.045], F)
+EDGE_OPTS = dict(cov_scale=1.5, sigma_xy_min=0.007, sigma_theta_min=0.0036)
+EDGE_POSE = np.array([11.5, 9.25, EDGE_REF + 0.13], F)
+# the shard whose global indices cross 2^24: rank 4097 of stride 4095 (2^24 - 1 = 4095 * 4097), the job's last, 65 particles
+EDGE_SHARD = dict(global_offset=(1 << 24) - 1, global_n=(1 << 24) - 1 + 65, shard_stride=4095)
+NAN_AT, INF_AT = 70, 200
+
+
+def edge_cases():
+    """name -> dict(n, x, y, th, w, pose, frame, delta, cov, ref_theta, opts, goff): what the issue's list of edges asks for, each a
+    variation of the stage test's case (a full covariance, a scale, both floors, frame 9, headings ref_theta +- 0.2, positions in [8, 16))."""
+    def case(seed, n=EDGE_N, ref=EDGE_REF, spread=0.2, centre=None, lo=8.0, hi=16.0, pose=None, frame=EDGE_FRAME, delta=EDGE_DELTA,
+             cov=CORRIDOR_COV, opts=EDGE_OPTS, goff=0):
+        x, y, th, w = cloud(n, ref if centre is None else centre, spread, seed, lo, hi)
+        pose = np.array([0.5 * (lo + hi), 0.25 * lo + 0.75 * hi, (ref if centre is None else centre) + 0.13], F) if pose is None else pose
+        return dict(n=n, x=x, y=y, th=th, w=w, pose=pose, frame=frame, delta=delta, cov=cov, ref_theta=float(ref), opts=dict(opts), goff=goff)
+
+    c = {
+        "headings all round": case(11, spread=np.pi),
+        "phi near +100": case(12, ref=-50.0, centre=50.0, spread=0.5),
+        "phi near -100": case(13, ref=50.0, centre=-50.0, spread=0.5),
+        "phi near +1100": case(14, ref=-550.0, centre=550.0, spread=0.5),
+        "phi near -1100": case(15, ref=550.0, centre=-550.0, spread=0.5),
+        "ref_theta +1000": case(16, ref=1000.0),
+        "ref_theta -1000": case(17, ref=-1000.0),
+        "positions to 2000": case(18, lo=-2000.0, hi=2000.0),
+        "positions below 1e-3": case(19, lo=-1e-3, hi=1e-3),
+        "first pivot 0": case(20, cov=np.array([0, 0, 0, 0.01, 0.001, 0.0004], F), opts={}),
+        "rank 1": case(21, cov=np.array([4, 2, 1, 1, 0.5, 0.25], F) * F(0.0009765625), opts={}),
+        "scale 0": case(22, opts=dict(cov_scale=0.0, sigma_theta_min=0.01)),
+        "frame 0": case(23, frame=0),
+        "frame 1": case(24, frame=1),
+        "frame 4194303": case(25, frame=4194303),
+        "indices across 2^24": case(26, n=65, goff=EDGE_SHARD["global_offset"]),
+    }
+    L, _ = factor(c["first pivot 0"]["cov"])
+    assert (L[[0, 1, 3]] == 0).all() and (L[[2, 4, 5]] != 0).all()
+    L, _ = factor(c["rank 1"]["cov"])
+    assert L[0] != 0 and L[1] != 0 and L[3] != 0 and (L[[2, 4, 5]] == 0).all()           # p1 and p2 are exactly 0
+    L, _ = factor(c["scale 0"]["cov"], **c["scale 0"]["opts"])
+    assert (L[:5] == 0).all() and L[5] == F(0.01)
+    for name, least in (("phi near +100", 99), ("phi near -100", 99), ("phi near +1100", 1099), ("phi near -1100", 1099)):
+        k = c[name]
+        assert (np.sign(k["th"]) == -np.sign(k["ref_theta"])).all() and np.abs(k["th"] - F(k["ref_theta"])).min() > least
+    return c
+
+
+def edge_want(k):
+    """(x', y', theta', pose') of an edge case by the restatement."""
+    x, y, th = move(k["x"], k["y"], k["th"], k["frame"], k["delta"], k["cov"], k["ref_theta"], goff=k["goff"], **k["opts"])
+    return x, y, th, move_pose(k["pose"], k["delta"], k["cov"], k["ref_theta"], **k["opts"])
 
 
 _STAT = {}

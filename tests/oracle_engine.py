@@ -140,6 +140,13 @@ class OracleShardEngine:
         self.x += d[0]; self.y += d[1]; self.th += d[2]
         self.robot += d
 
+    def move_particles(self, frame, delta, cov=None, **opts):
+        """pfslam_move_particles restated (tests/move_ref.py), the draw keyed by the global index; the weights and their mirror stay."""
+        import move_ref as M
+        x, y, th = M.move(self.x, self.y, self.th, frame, delta, cov, goff=self.goff, **opts)
+        self.x[:], self.y[:], self.th[:] = x, y, th
+        self.robot[:] = M.move_pose(self.robot, delta, cov, **opts)
+
     def maybe_balance(self, frame):
         if self.period > 0 and frame % self.period == 5 and self.size > 0:
             O.lib().orc_kd_balance(O.P(self.tree), self.size)

@@ -110,6 +110,7 @@ def lib():
     L.orc_slam_grid.restype = vp; L.orc_slam_grid.argtypes = [vp]
     L.orc_slam_set_particles.restype = None; L.orc_slam_set_particles.argtypes = [vp, vp]
     L.orc_slam_shift_particles.restype = None; L.orc_slam_shift_particles.argtypes = [vp, vp]
+    L.orc_slam_replace_poses.restype = None; L.orc_slam_replace_poses.argtypes = [vp, vp, vp, vp, vp]
     L.orc_slam_get_pose.restype = None; L.orc_slam_get_pose.argtypes = [vp, vp]
     L.orc_slam_kd_size.restype = i32; L.orc_slam_kd_size.argtypes = [vp]
     L.orc_slam_tree.restype = vp; L.orc_slam_tree.argtypes = [vp]
@@ -257,6 +258,11 @@ class Slam:
 
     def shift_particles(self, delta):
         lib().orc_slam_shift_particles(self.h, P(np.ascontiguousarray(delta, dtype=np.float32)))
+
+    def replace_poses(self, x, y, theta, robot):
+        x, y, theta, robot = (np.ascontiguousarray(v, dtype=np.float32) for v in (x, y, theta, robot))
+        assert len(x) == len(y) == len(theta) == self.n and len(robot) == 3
+        lib().orc_slam_replace_poses(self.h, P(x), P(y), P(theta), P(robot))
 
     def step_grid(self, frame, scan):
         scan = np.ascontiguousarray(scan, dtype=np.float32)

@@ -52,6 +52,9 @@ class StageShadow:
     def set_grid(self, grid):
         self.h.set_grid(grid)
 
+    def move_particles(self, frame, delta, cov=None, **opts):
+        self.h.move_particles(frame, delta, cov, **opts)
+
     def motion_update(self, frame):
         """(the warm-up dispersions some tests put in front of their first frame)"""
         self.h.motion_update(frame)

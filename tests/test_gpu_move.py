@@ -1,6 +1,7 @@
 """pfslam_move_particles on the GPU: the stage on uploaded clouds against the restatement (tests/move_ref.py, held to the header by
-tests/test_move_spec.py) bit for bit, the device-library trigonometry within an ulp of it, sharded handles, the ordering behind frames in
-flight in every frame mode, the heading bound, the refusals and the C++ host layer.
+tests/test_move_spec.py) bit for bit, also at the edges of its inputs (section 1b), the device-library trigonometry within an ulp of it,
+sharded handles, the ordering behind frames in flight in every frame mode, the heading bound, the refusals and the C++ host layer.
+Frames with moves against the CPU oracle are in tests/test_gpu_move_frames.py.
 
 Apart from the device-library case, whose bound is derived in its docstring, every comparison is bit for bit."""
 import ctypes as C
@@ -112,6 +113,83 @@ def test_stage_with_the_device_library_is_within_an_ulp(pkg):
     print("pose: %s ulp" % dp.tolist())
     assert worst <= 1 and dp.max() <= 1
     assert (bits(res[1][0]["w"]) == bits(w)).all()
+
+
+# ---- 1b. the stage's inputs at their edges (the same set runs the kernel text on the CPU: tests/test_move_kernel_text.py) --------------------
+EDGES = M.edge_cases()
+
+
+def staged_edge(pkg, k, x=None, th=None):
+    """One call on a fresh handle with the case's cloud and pose uploaded: (particles, pose)."""
+    kw = dict(M.EDGE_SHARD) if k["goff"] else {}
+    assert kw.get("global_offset", 0) == k["goff"]
+    h = pkg.PfSlam(k["n"], **kw)
+    h.set_particles(M.particles_of(k["x"] if x is None else x, k["y"], k["th"] if th is None else th, k["w"]))
+    h.set_pose(k["pose"])
+    h.move_particles(k["frame"], k["delta"], k["cov"], k["ref_theta"], **k["opts"])
+    out = h.particles(), np.array(h.pose, F)
+    h.close()
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_stage_at_the_edges_of_its_inputs(pkg, name):
+    """257 particles (65 for the shard) against the restatement bit for bit: headings +-pi around ref_theta; |phi| near 100 and 1100 rad
+    with headings and ref_theta of opposite sign; ref_theta of +-1000; positions in [-2000, 2000) and below 1e-3; a first pivot of exactly
+    0, a rank-1 covariance (p1 = p2 = 0) and cov_scale 0 with sigma_theta_min alone; frames 0, 1 and 4 194 303; and the last shard of a
+    job of 2^24 + 64 particles, whose global indices 16 777 215 .. 16 777 279 cross 2^24."""
+    k = EDGES[name]
+    got, pose = staged_edge(pkg, k)
+    wx, wy, wt, wpose = M.edge_want(k)
+    same_particles(got, M.particles_of(wx, wy, wt, k["w"]), name)
+    assert (bits(pose) == bits(wpose)).all(), (name, pose, wpose)
+    moved = bits(got["theta"]) != bits(k["th"])
+    assert moved.sum() >= k["n"] - 2, name                      # (every heading got its increment, but for one that rounds away)
+
+
+def test_stage_without_noise_is_the_shift_on_the_device(pkg):
+    """cov NULL, zero floors, every heading equal to ref_theta: pfslam_shift_particles(delta) on a second handle, bit for bit, particles and
+    pose; operands that are not signed zeros, and the restatement agrees with both."""
+    n, ref = M.EDGE_N, F(0.83)
+    x, y, _, w = M.cloud(n, seed=31)
+    p = M.particles_of(x, y, np.full(n, ref, F), w)
+    delta = np.array([0.5, -0.125, 0.07], F) + F(1e-3)
+    pose = np.array([3.0, -2.0, ref], F)
+    res = []
+    for call in ("move", "shift"):
+        h = pkg.PfSlam(n)
+        h.set_particles(p)
+        h.set_pose(pose)
+        if call == "move":
+            h.move_particles(5, delta, None, float(ref))
+        else:
+            h.shift_particles(delta)
+        res.append((h.particles(), np.array(h.pose, F)))
+        h.close()
+    same_particles(res[0][0], res[1][0], "move against shift")
+    assert (bits(res[0][1]) == bits(res[1][1])).all()
+    wx, wy, wt = M.move(x, y, p["theta"], 5, delta, None, float(ref))
+    same_particles(res[0][0], M.particles_of(wx, wy, wt, w), "move against the restatement")
+    assert not (bits(res[0][0]["x"]) == bits(x)).any()
+
+
+def test_a_particle_that_is_not_finite_stays_so_and_keeps_to_itself(pkg):
+    """One particle has a NaN heading, another x = +inf: every field the NaN heading enters is NaN, x stays +inf and that particle's y and
+    heading are the restatement's; all other particles and the pose equal the restatement bit for bit."""
+    k = EDGES["headings all round"]
+    th, x = k["th"].copy(), k["x"].copy()
+    th[M.NAN_AT], x[M.INF_AT] = np.nan, np.inf
+    got, pose = staged_edge(pkg, k, x=x, th=th)
+    wx, wy, wt, wpose = M.edge_want(k)
+    assert np.isnan(got["x"][M.NAN_AT]) and np.isnan(got["y"][M.NAN_AT]) and np.isnan(got["theta"][M.NAN_AT])
+    assert np.isinf(got["x"][M.INF_AT]) and got["x"][M.INF_AT] > 0
+    rest = np.ones(k["n"], bool)
+    rest[M.NAN_AT] = False
+    assert (bits(got["y"][rest]) == bits(wy[rest])).all() and (bits(got["theta"][rest]) == bits(wt[rest])).all()
+    rest[M.INF_AT] = False
+    assert (bits(got["x"][rest]) == bits(wx[rest])).all()
+    assert (bits(got["w"]) == bits(k["w"])).all()
+    assert (bits(pose) == bits(wpose)).all()
 
 
 # ---- 2. sharded handles ------------------------------------------------------------------------------------------------------------------

@@ -200,6 +200,10 @@ class _VirtualRanks:
         for e in self.engs:
             e.shift_particles(d)
 
+    def move_particles(self, frame, delta, cov=None, **opts):
+        for e in self.engs:
+            e.move_particles(frame, delta, cov, **opts)
+
     def step(self, f, scan):
         torch, engs, bufs = self.torch, self.engs, self.bufs
         seeded = [e.shard_disperse(f, scan) for e in engs]
